@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — decode throughput of the paged-attention hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline figure, prefill of the timed batch, step share of the
+HBM roofline).  --dump-outputs DIR also writes what the last timed step returned (tokens.npy, logits.npy).  Every other measurement below
+— roofline of the dominant kernel, counter passes, other models / batches / precisions, the CPU baseline — takes runs of its own and is made
+only with --full.
 
 Workload (BASELINE.json configs[1]): Qwen3-0.6B shape, fp16, synthetic random-init weights, 32
 sequences with 1024-token synthetic prompts, greedy decode, block size 256, hipGraph decode steps.
@@ -19,7 +24,7 @@ rank: the multi-GPU path cannot be exercised on the 1-GPU development boxes, and
 measurement already taken — if it fails twice (with and without the peer-to-peer kernels), the replicas number is
 reported as `value`, labelled as such, with the error attached.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     — the dominant kernel (paged decode attention): algorithmic K/V bytes per launch
                  divided by its average launch duration, measured here with HIP events on the
                  kernel's own stream over back-to-back launches on the live KV pool (all layers
@@ -548,7 +553,7 @@ def _pmc_child(model: str, counters, steps: int, warm: int, timeout_s: float = 2
         return "this process already runs under a profiler"
     out = tempfile.mkdtemp(prefix="nvr_pmc_", dir="/tmp")
     cmd = [exe, "--kernel-trace", "--pmc", *counters, "--output-format", "csv", "-d", out, "-o", "pmc", "--",
-           sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warm), "--model", model, "--no-cpu-baseline", "--no-chain",
+           sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warm), "--model", model, "--full", "--no-cpu-baseline", "--no-chain",
            "--no-shared-prefix", "--no-configs3", "--no-prefill-sweep", "--no-batch-sweep", "--no-default-engine", "--sync-decode", "--eager",
            "--no-live-pmc", "--attn-reps", "1"]
     try:
@@ -672,6 +677,13 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also make every side measurement of the line (each a run of its own after the timed steps: roofline of the dominant kernel and of the "
+                         "GEMM chain, the rocprofv3 counter passes, configs[2] / [3] / [4], batch sweep, ragged / stochastic / bf16 / f32 / default-engine "
+                         "blocks, the CPU baseline); default: the headline measurement only.  The --no-* options below switch single blocks of --full off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR: tokens.npy (the sampled token id of every sequence, float64) "
+                         "and logits.npy (the f32 logits of every sequence, rank 0's vocabulary shard under tensor parallelism); same arguments, same files")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--attn-reps", type=int, default=8)
     ap.add_argument("--no-chain", action="store_true", help="skip the GEMM / norm chain timing (roofline_chain)")
@@ -699,6 +711,8 @@ def main() -> None:
                     help="do not run the child rocprofv3 --pmc FETCH_SIZE pass that counts roofline.traffic in this run (N = 1; "
                          "NVR_BENCH_LIVE_PMC=0 does the same): the committed pass under profiles/ is quoted instead")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global BATCH, PROMPT_LEN
     BATCH, PROMPT_LEN = MODELS[args.model]["batch"], MODELS[args.model]["prompt_len"]
     # Control-plane dry runs of 4 / 8 rank PROCESSES on ONE GPU only (tools/tp_dryrun.sh, NRANKS >= 4): every cross-process rendezvous of a one-shot collective
@@ -712,7 +726,7 @@ def main() -> None:
         os.environ["NVR_LAZY_LOGITS"] = "0"
 
     live_pmc = live_prefill = None
-    if args.gpus == 1 and not args.no_live_pmc and os.environ.get("NVR_BENCH_LIVE_PMC", "1") != "0" and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.full and args.gpus == 1 and not args.no_live_pmc and os.environ.get("NVR_BENCH_LIVE_PMC", "1") != "0" and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         live_pmc = live_pmc_attention(args.model)                                # child processes, before this one initialises the GPU
         live_prefill = live_pmc_prefill(args.model)
     nvr = nvr_import.load()                # loads libnvr.so (and the ROCm HIP runtime)
@@ -828,10 +842,18 @@ def main() -> None:
         crc = 0
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            toks = array.array("q", eng.step()["tokens"]).tobytes()                     # (~1 us of host time per step, next to a 1.4 ms step)
+            info = eng.step()
+            toks = array.array("q", info["tokens"]).tobytes()                           # (~1 us of host time per step, next to a 1.4 ms step)
             crc = zlib.crc32(toks, crc); scrc = zlib.crc32(toks, scrc)
         nvr.synchronize()
         el = time.perf_counter() - t0
+        if args.dump_outputs:
+            # what a caller of the last timed step holds: its tokens, and the logits the runner hands out on request (every rank asks, rank 0 writes)
+            logits = eng.model_runner.logits(BATCH)
+            if rank == 0:
+                os.makedirs(args.dump_outputs, exist_ok=True)
+                np.save(os.path.join(args.dump_outputs, "tokens.npy"), np.asarray(info["tokens"], np.float64))
+                np.save(os.path.join(args.dump_outputs, "logits.npy"), logits)
         token_crc[0] = crc; stream_crc[0] = scrc
         h1 = eng.host_times()
         host_us[0] = {k: round((h1[k + "_us"] - h0[k + "_us"]) / max(1, h1["steps"] - h0["steps"]), 2) for k in ("schedule", "postprocess")}
@@ -973,7 +995,9 @@ def main() -> None:
                 for k in [k for k in env if k.startswith("TORCHELASTIC_")]:   # (the children are plain processes, not the launcher agent's workers)
                     del env[k]
                 cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
-                       "--parallel", "tp", "--no-cpu-baseline", "--attn-reps", "1"] + (["--eager"] if args.eager else [])
+                       "--parallel", "tp", "--no-cpu-baseline", "--attn-reps", "1"] + (["--eager"] if args.eager else []) + (["--full"] if args.full else [])
+                if args.dump_outputs:                                        # (the value of the line is the tensor-parallel engine's: so are the outputs)
+                    cmd += ["--dump-outputs", args.dump_outputs]
                 child_out, child_err, child_rc = "", "", None
                 txt = lambda b: b.decode("utf-8", "replace") if isinstance(b, (bytes, bytearray)) else (b or "")   # noqa: E731
                 try:
@@ -1017,28 +1041,29 @@ def main() -> None:
     step_bytes = mb["weights"] + mb["kv_read"] + mb["kv_write"]
     step_gbs = step_bytes / (args.gpus / jobs) / (ms_per_step * 1e-3) / 1e9   # per-GPU share of the algorithmic bytes
 
-    attn = time_attention_kernel(nvr, eng, mc, args.attn_reps)
+    side = args.full and args.gpus == 1 and rank == 0 and args.model == "qwen3-0.6b"      # the side blocks of the N = 1 line
+    attn = time_attention_kernel(nvr, eng, mc, args.attn_reps) if args.full else None
     chain = None
-    if args.gpus == 1 and rank == 0 and not args.no_chain and args.model == "qwen3-0.6b":
+    if side and not args.no_chain:
         try:
             chain = time_decode_chain(nvr, mc)
         except Exception as ex:                                              # noqa: BLE001
             print(f"[bench] decode chain timing failed: {ex}", file=sys.stderr, flush=True)
     shared_prefix = None
-    if args.gpus == 1 and rank == 0 and not args.no_shared_prefix and args.model == "qwen3-0.6b":
+    if side and not args.no_shared_prefix:
         try:
             shared_prefix = shared_prefix_decode(nvr, mc)
         except Exception as ex:                                              # noqa: BLE001
             shared_prefix = {"error": str(ex)[:300]}
     configs3 = None
-    if args.gpus == 1 and rank == 0 and not args.no_configs3 and args.model == "qwen3-0.6b":
+    if side and not args.no_configs3:
         try:
             configs3 = side_decode(nvr, "qwen3-8b")
         except Exception as ex:                                              # noqa: BLE001
             configs3 = {"error": str(ex)[:300]}
-    configs3_tp = args.gpus > 1 and parallelism.startswith("tp") and not args.no_configs3 and args.model == "qwen3-0.6b"
+    configs3_tp = args.full and args.gpus > 1 and parallelism.startswith("tp") and not args.no_configs3 and args.model == "qwen3-0.6b"
     batch_sweep = None
-    if args.gpus == 1 and rank == 0 and not args.no_batch_sweep and args.model == "qwen3-0.6b":
+    if side and not args.no_batch_sweep:
         # the same engine path at larger batches: the step's share of the HBM roofline grows with the K/V bytes per launch
         batch_sweep = []
         for preset, bsz, plen in (("qwen3-0.6b", 64, 1024), ("qwen3-0.6b", 128, 1024), ("qwen3-0.6b", 256, 1024), ("qwen3-0.6b", 512, 1024),
@@ -1051,20 +1076,20 @@ def main() -> None:
             except Exception as ex:                                          # noqa: BLE001
                 batch_sweep.append({"model": preset, "batch": bsz, "error": str(ex)[:200]})
     ragged = None
-    if args.gpus == 1 and rank == 0 and not args.no_batch_sweep and args.model == "qwen3-0.6b":
+    if side and not args.no_batch_sweep:
         try:
             ragged = ragged_decode(nvr, mc)
         except Exception as ex:                                              # noqa: BLE001
             ragged = {"error": str(ex)[:300]}
     stochastic = None
-    if args.gpus == 1 and rank == 0 and not args.no_batch_sweep and args.model == "qwen3-0.6b":
+    if side and not args.no_batch_sweep:
         try:
             stochastic = stochastic_decode(nvr, mc, check=not args.no_cpu_baseline)
             stochastic["greedy_ms_per_step"] = round(ms_per_step, 4)
         except Exception as ex:                                              # noqa: BLE001
             stochastic = {"error": str(ex)[:300]}
     bf16_block = None
-    if args.gpus == 1 and rank == 0 and not args.no_batch_sweep and args.model == "qwen3-0.6b":
+    if side and not args.no_batch_sweep:
         # Config.dtype = "bfloat16" (config.rs:51,113-116): the same workload on the bf16 build of every kernel (same bytes, same MFMA rate)
         try:
             r = side_decode(nvr, "qwen3-0.6b", batch=BATCH, prompt_len=PROMPT_LEN, dtype="bfloat16")
@@ -1072,7 +1097,7 @@ def main() -> None:
         except Exception as ex:                                              # noqa: BLE001
             bf16_block = {"error": str(ex)[:200]}
     default_engine = None
-    if args.gpus == 1 and rank == 0 and not args.no_default_engine and args.model == "qwen3-0.6b":
+    if side and not args.no_default_engine:
         # the headline engine IS the engine nvr_config_default builds (r05: async_decode defaults to 1); measured again here on a fresh engine of
         # its own, next to the opt-out (async_decode = 0: the host waits for every step's tokens before it schedules the next step) and the
         # prefill on a recycled free list (block tables, not contiguous rows)
@@ -1110,22 +1135,24 @@ def main() -> None:
         except Exception as ex:                                              # noqa: BLE001
             default_engine["prefill_recycled_free_list"] = {"error": str(ex)[:200]}
     f32_block = None
-    if args.gpus == 1 and rank == 0 and not args.no_default_engine and args.model == "qwen3-0.6b":
+    if side and not args.no_default_engine:
         try:
             f32_block = float32_path(nvr)
         except Exception as ex:                                              # noqa: BLE001
             f32_block = {"error": str(ex)[:200]}
     sweep = None
-    if args.gpus == 1 and rank == 0 and not args.no_prefill_sweep and args.model == "qwen3-0.6b":
+    if side and not args.no_prefill_sweep:
         try:
             sweep = prefill_sweep(nvr)
         except Exception as ex:                                              # noqa: BLE001
             sweep = {"error": str(ex)[:300]}
-    achieved = attn["alg_bytes"] / (attn["us_per_launch"] * 1e-6) / 1e9
+    achieved = attn["alg_bytes"] / (attn["us_per_launch"] * 1e-6) / 1e9 if attn else None
     traffic = None
     pmc_path = os.path.join(ROOT, "profiles", "pmc_attn_latest.json")
     traffic_live = isinstance(live_pmc, dict)
-    if traffic_live:
+    if attn is None:
+        pass                                                             # (a plain run: no roofline block to attach a traffic figure to)
+    elif traffic_live:
         traffic = int(round(live_pmc["traffic_over_algorithmic"] * attn["alg_bytes"]))
     elif os.path.exists(pmc_path):
         try:
@@ -1161,13 +1188,16 @@ def main() -> None:
                                 "mfma_busy_frac_pmc_source)"},
             "step_hbm_frac": round(step_gbs / HBM_PEAK_GBS, 4),
             "step_algorithmic_bytes": int(step_bytes),
-            "roofline": {"kernel": "attn_rows_kernel (paged decode attention, K9)", "bound": "hbm", "achieved": round(achieved, 1),
+            "roofline": None if attn is None else
+                        {"kernel": "attn_rows_kernel (paged decode attention, K9)", "bound": "hbm", "achieved": round(achieved, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                          "us_per_launch": round(attn["us_per_launch"], 2), "launches_timed": attn["launches"],
                          "timed_as": "one captured graph of the launches, replayed (like the step)" if attn.get("as_graph") else "eager back-to-back launches",
                          "algorithmic_bytes_per_launch": int(attn["alg_bytes"])},
         }
-        if traffic_live:
+        if attn is None:
+            pass
+        elif traffic_live:
             out["roofline"]["traffic_source"] = ("counted in this run: a child `rocprofv3 --kernel-trace --pmc FETCH_SIZE` pass of eager decode steps "
                                                  "(FETCH_SIZE KiB x 1024 x 2 on gfx950), HBM bytes / algorithmic bytes over its attention dispatches, "
                                                  "scaled to the algorithmic bytes of the timed launches")
@@ -1223,7 +1253,7 @@ def main() -> None:
             out["float32_path"] = f32_block
         if sweep is not None:
             out["prefill_sweep"] = sweep
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         if replicas is not None and tensor_parallel is not None and "error" not in tensor_parallel:
             # N > 1: the tensor-parallel engine's line is the result; the replicas measured on the same ranks ride along

@@ -8,7 +8,10 @@ import sys
 
 # in-process tensor-parallel tests drive up to 8 ranks of one process on one GPU, each on its own stream, and their one-shot
 # collectives wait for each other INSIDE kernels: every stream needs a hardware queue of its own (HIP's default is 4 per process)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# — a smaller value inherited from the environment (some machines export 4) is raised: with it the tp >= 4 peer-to-peer tests wait for
+# ranks whose kernels never get a queue until their collectives time out.  The HIP runtime reads it when libnvr.so first initialises it.
+if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

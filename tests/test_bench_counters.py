@@ -1,7 +1,13 @@
 """bench.py's in-run counter passes (roofline.traffic, prefill.mfma_busy_frac_pmc): the parsing of rocprofv3's counter table is pure and is
 checked here on synthetic tables; the passes themselves run on the GPU box inside the bench."""
 import importlib.util
+import json
 import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 spec = importlib.util.spec_from_file_location("nvr_bench", os.path.join(ROOT, "bench.py"))
@@ -58,3 +64,26 @@ def test_prefill_busy_share_takes_the_last_prefill_step_only():
     assert got["per_kernel"]["qkv+RoPE+store"] == 0.4 and got["per_kernel"]["flash_prefill"] == 0.3 and got["per_kernel"]["o / down + residual"] == 0.5
     busy = 3 * (400 + 300 + 500) * 1024; cyc = 1000 + 3 * (3 * 1000 + 100)
     assert abs(got["step_weighted"] - busy / (1024 * cyc)) < 1e-3 and got["dispatches"] == 1 + 3 * 4
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_given_steps_and_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` makes the headline measurement only (no side block, `roofline` null), reports the K it was
+    given and a positive ms_per_step, and with --dump-outputs writes the last timed step's tokens and logits: same arguments, same arrays."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"dump{i}"
+        cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)],
+                            check=True, stdout=subprocess.PIPE, text=True, timeout=300, cwd=str(tmp_path))
+        line = json.loads([l for l in cp.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "tokens/s" and line["higher_is_better"] is True
+        assert abs(line["value"] - bench.MODELS["qwen3-0.6b"]["batch"] / line["ms_per_step"] * 1e3) < 1e-2 * line["value"]
+        assert line["roofline"] is None and not {"cpu_baseline", "configs3", "batch_sweep", "prefill_sweep", "roofline_chain", "bf16", "float32_path"} & set(line)
+        assert sorted(os.listdir(d)) == ["logits.npy", "tokens.npy"]
+        dumps.append({n: np.load(d / n) for n in os.listdir(d)})
+    B, V = bench.MODELS["qwen3-0.6b"]["batch"], 151936
+    a, b = dumps
+    assert a["tokens.npy"].dtype == np.float64 and a["tokens.npy"].shape == (B,) and a["logits.npy"].dtype == np.float32 and a["logits.npy"].shape == (B, V)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20 and np.isfinite(a["logits.npy"]).all()
+    assert np.array_equal(a["logits.npy"].argmax(1), a["tokens.npy"].astype(np.int64))           # greedy: the tokens are the arg-max of the dumped logits
+    assert all(np.array_equal(a[n], b[n]) for n in a)

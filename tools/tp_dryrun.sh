@@ -10,6 +10,7 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export NVR_BENCH_SHARED_GPU=1 GPU_MAX_HW_QUEUES=16
 port=29610
+BENCH_ARGS="--full $BENCH_ARGS"        # the configs[3] tensor-parallel side block is part of the flow under test: a plain run leaves it out
 run() {
     name=$1; shift
     port=$((port + 10))
