@@ -125,6 +125,14 @@ typedef struct nvr_config {
                                           arithmetic of the reference's own CPU path: its logits to ~1e-5.  nvr_runner_copy_weight then
                                           returns f32 values (two 16-bit words per element).  The stateless op entry points
                                           (nvr_linear, nvr_paged_attn_*, ...) take their 16-bit type from nvr_ops_set_dtype */
+    char kv_cache_dtype[16];           /* extension (the reference's cache has the model dtype, model_runner.rs:364-396): "" | "auto" (default): the KV cache
+                                          has the runner's dtype; "fp8" | "fp8_e4m3": the cache holds OCP e4m3 bytes (half the K/V bytes per decode step,
+                                          twice the blocks per HBM budget with num_kvcache_blocks = -2), value = byte * scale with one k_scale and one
+                                          v_scale per runner (nvr_runner_set_kv_scales, default 1.0).  Such a runner writes the cache with nvr_kv_store_fp8,
+                                          decodes with nvr_paged_attn_decode_fp8, and its prefill attention reads K/V from the step's own projections: it
+                                          needs recompute_cached_prefix = 1, enable_chunked_prefill = 0 and a 16-bit dtype, head_dim 64 / 128 and 1, 2 or 4
+                                          query heads per kv head (NVR_ERR_UNSUPPORTED otherwise); it never takes the shared-prefix or the work-balanced
+                                          decode launch.  Anything else: NVR_ERR_INVALID_ARG ("Unsupported kv_cache_dtype: ...") */
 } nvr_config;
 NVR_API void nvr_config_default(nvr_config *cfg);                    /* config.rs:54-71 */
 NVR_API int nvr_config_validate(const nvr_config *cfg);              /* config.rs:83-119 */
@@ -257,8 +265,15 @@ NVR_API int nvr_runner_load_tensor(nvr_model_runner_t *r, const char *name, int 
 NVR_API int nvr_runner_copy_weight(nvr_model_runner_t *r, const char *local_name, uint16_t *host_out, size_t cap_elems,
                                    int64_t *rows, int64_t *cols);
 NVR_API uint64_t nvr_runner_num_kvcache_blocks(const nvr_model_runner_t *r);
-/* KV pool of layer l (borrowed device pointers, fp16 [NB, bs, KVH/tp, D], model_runner.rs:364-396) */
+/* KV pool of layer l (borrowed device pointers, [NB, bs, KVH/tp, D] elements of nvr_runner_kv_cache_dtype — the runner's dtype, or one
+ * e4m3 BYTE per element for nvr_config.kv_cache_dtype = "fp8"; model_runner.rs:364-396) */
 NVR_API int nvr_runner_kv_cache(nvr_model_runner_t *r, size_t layer, void **k_dev, void **v_dev);
+/* element type of that pool: "float16" | "bfloat16" | "float32" | "fp8_e4m3" (create_kv_cache's dtype argument, model_runner.rs:364-396) */
+NVR_API const char *nvr_runner_kv_cache_dtype(const nvr_model_runner_t *r);
+/* scales of an fp8 KV cache (stored byte = e4m3(x / scale), both default 1.0; model_runner.rs:364-396 has no counterpart): before the
+ * first step only — the cache rows already written hold the old scales (NVR_ERR_INVARIANT afterwards; NVR_ERR_INVALID_ARG unless both are
+ * positive and finite; NVR_ERR_UNSUPPORTED on a runner whose cache is not fp8) */
+NVR_API int nvr_runner_set_kv_scales(nvr_model_runner_t *r, float k_scale, float v_scale);
 NVR_API void *nvr_runner_stream(nvr_model_runner_t *r);
 /* diagnostic: re-launch the hipGraph of the last decode step n times back to back (same inputs, no host round trip; the caller
  * synchronises): the GPU's launch chain without the host gap between engine steps (execute_with_cuda_graph, model_runner.rs:303-326) */
@@ -576,6 +591,20 @@ NVR_API int nvr_paged_attn_decode_shared(const nvr_half *q, int64_t ldq, const n
                                          const nvr_attn_meta *meta, int64_t H, int64_t KVH, int64_t D, int64_t block_size,
                                          float scale, int64_t shared_len, const int32_t *rows, const int32_t *kv0, const int32_t *count,
                                          nvr_half *out, void *workspace, void *stream);
+/* FP8 (OCP e4m3fn) KV cache, the store half of attention.rs:150-174: the roped K and V columns of the packed qkv buffer [T, (H+2KVH)*D] (16-bit,
+ * nvr_ops_set_dtype; "float32": NVR_ERR_UNSUPPORTED) go to the byte caches [NB, bs, KVH, D] at slot_mapping (< 0 skips the row): byte =
+ * e4m3(x / scale), round to nearest even, clamped to +-448 (no NaN / infinity is ever produced from finite input) */
+NVR_API int nvr_kv_store_fp8(const nvr_half *qkv, const int32_t *slot_mapping, int64_t T, int64_t H, int64_t KVH, int64_t D,
+                             float k_scale, float v_scale, uint8_t *k_cache, uint8_t *v_cache, void *stream);
+/* K9 over such caches (attention.rs:225-235,264-318, A-8: the semantics of nvr_paged_attn_decode with K = k_scale * bytes, V = v_scale * bytes;
+ * k_scale is folded into the softmax scale, v_scale multiplies the finished row).  D in {64, 128}, H / KVH in {1, 2, 4}, block_size at least one
+ * row group of the kernel (8 rows at D = 128, 16 at D = 64); other shapes and "float32": NVR_ERR_UNSUPPORTED.  workspace:
+ * nvr_paged_attn_workspace_bytes.  tickets: accepted for symmetry with nvr_paged_attn_decode_fused and not used (split contexts are
+ * merged by a second launch); may be NULL. */
+NVR_API int nvr_paged_attn_decode_fp8(const nvr_half *q, int64_t ldq, const uint8_t *k_cache, const uint8_t *v_cache,
+                                      const nvr_attn_meta *meta, int64_t H, int64_t KVH, int64_t D, int64_t block_size,
+                                      float scale, float k_scale, float v_scale, nvr_half *out, void *workspace,
+                                      uint32_t *tickets /* nullable */, void *stream);
 /* K7 varlen causal prefill attention, attention.rs:177-208 (q,k,v inside packed qkv, stride ld) */
 NVR_API int nvr_attn_prefill_varlen(const nvr_half *q, const nvr_half *k, const nvr_half *v, int64_t ld,
                                     const nvr_attn_meta *meta, int64_t T, int64_t H, int64_t KVH, int64_t D,

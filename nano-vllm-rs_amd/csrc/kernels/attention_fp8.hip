@@ -1,0 +1,419 @@
+// attention_fp8.hip — the FP8 (OCP e4m3fn) KV cache for gfx950: the quantising store (kv_store_fp8) and paged decode attention over
+// byte caches (attention_fp8).  Semantics of the decode kernel are those of attention.hip's (query t sees exactly
+// ctx_lens[t] keys, softmax in f32, the G = H/KVH query heads of a kv head together); reference call site
+// Attention::flash_attention_decode, src/layers/attention.rs:225-235, cache rows :150-174.
+//
+// Format: caches [NB, bs, KVH, D] BYTES; one k_scale and one v_scale (f32) per call: stored byte = e4m3(x / scale), value read =
+// byte * scale.  k_scale is folded into the softmax scale and v_scale multiplies a workgroup's finished f32 sums once (in front of the
+// division by the softmax sum, or of the merge of the partitions, which is linear in them), so neither is seen by the inner loop.
+//
+// Geometry (its own, not attn_rows_kernel's): a K / V row of one kv head is D bytes; a lane holds 16 of them (one 16-byte request),
+// so a row is D/16 lanes (8 at D = 128, 4 at D = 64) and one wave-instruction reads 64/(D/16) rows = 1 KiB: 8 tokens at D = 128, 16 at
+// D = 64 — twice the tokens per request of the 16-bit kernel.  Requests go straight to VGPRs, non-temporal, U row groups of K and of V
+// back to back before any arithmetic.  Dequantisation is in registers: K bytes -> packed 16-bit pairs (v_cvt_scalef32_pk_f16_fp8 /
+// _bf16_fp8, scale operand 1.0) -> v_dot2 against the q pairs; V bytes -> f32 pairs (v_cvt_pk_f32_fp8) -> f32 FMA.  The butterfly of a
+// row's dot product runs over D/16 lanes and the 64/(D/16) row-group slots of a wave are merged once, at the end.
+#include <algorithm>
+#include <type_traits>
+#include "kernels.h"
+#include "device_utils.h"
+#include "attn_merge.h"
+#include "../common.h"
+
+namespace nvr { namespace NVR_DT_NS {
+
+typedef unsigned int uint4_t __attribute__((ext_vector_type(4)));
+
+// ---- kv_store_fp8 ----------------------------------------------------------------------------------------------------------------
+// e4m3 of x: round to nearest even, clamped to +-448 in front of the conversion (v_cvt_pk_fp8_f32 saturates or not by a mode bit)
+__device__ __forceinline__ float clamp448(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
+
+// One lane = 16 consecutive elements of the K or the V part of one token's qkv row -> one 16-byte store into the byte cache.
+__global__ __launch_bounds__(256) void kv_store_fp8_kernel(const half_t *__restrict__ qkv, const int32_t *__restrict__ slots, int64_t T, int H, int KVH, int D,
+                                                           float k_scale, float v_scale, uint8_t *__restrict__ kc, uint8_t *__restrict__ vc) {
+    const int per_kv = KVH * D / 16, per_tok = 2 * per_kv;              // 16-element pieces of a token's K (or V) columns / of both
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= T * per_tok) return;
+    const int64_t t = idx / per_tok;
+    const int c = (int)(idx - t * per_tok);
+    const bool is_v = c >= per_kv;
+    const int e0 = (is_v ? c - per_kv : c) * 16;                         // first element inside the token's [KVH, D] row
+    const int slot = slots[t];
+    if (slot < 0) return;
+    const half_t *src = qkv + t * (int64_t)(H + 2 * KVH) * D + (int64_t)(H + (is_v ? KVH : 0)) * D + e0;
+    const half8_t a = *reinterpret_cast<const half8_t *>(src), b = *reinterpret_cast<const half8_t *>(src + 8);
+    const float sc = is_v ? v_scale : k_scale;
+    float x[16];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { x[j] = clamp448((float)a[j] / sc); x[8 + j] = clamp448((float)b[j] / sc); }
+    uint4_t w;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int r = 0;
+        r = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * j], x[4 * j + 1], r, false);
+        r = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * j + 2], x[4 * j + 3], r, true);
+        w[j] = (unsigned int)r;
+    }
+    *reinterpret_cast<uint4_t *>((is_v ? vc : kc) + (int64_t)slot * KVH * D + e0) = w;
+}
+
+int kv_store_fp8(const half_bits *qkv, const int32_t *slots, int64_t T, int64_t H, int64_t KVH, int64_t D, float k_scale, float v_scale,
+                 uint8_t *k_cache, uint8_t *v_cache, hipStream_t s) {
+    if (T == 0) return 0;
+    if (D % 16 || !(k_scale > 0.f) || !(v_scale > 0.f))
+        return nvr::fail(NVR_ERR_INVALID_ARG, "kv_store_fp8: head_dim %ld (a multiple of 16), scales %g / %g (positive)", (long)D, k_scale, v_scale);
+    const int64_t n = T * 2 * KVH * D / 16;
+    kv_store_fp8_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>((const half_t *)qkv, slots, T, (int)H, (int)KVH, (int)D, k_scale, v_scale,
+                                                                                 k_cache, v_cache);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "kv_store_fp8 launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// ---- attention_fp8 ---------------------------------------------------------------------------------------------------------------
+struct AttnFp8Params {
+    const half_t *q; int64_t ldq;
+    const uint8_t *k, *v;
+    const int32_t *ctx_lens, *block_tables;
+    int32_t max_blocks, block_size, bs_shift;
+    int32_t H, KVH;
+    float scale;                       // softmax scale x k_scale
+    float v_scale;
+    int32_t part_size, num_parts;
+    float *part_o; float *part_ml;     // [nq, H, num_parts, D], [nq, H, num_parts, 2]
+    half_t *out;                       // [nq, H, D]
+};
+
+// 4 e4m3 bytes of w -> two packed 16-bit pairs (bytes 0,1 and 2,3) of the build's type, exactly (every e4m3 value is an fp16 and a bf16 value)
+__device__ __forceinline__ void fp8x4_to_half2(unsigned int w, half2_t &lo, half2_t &hi) {
+#ifdef NVR_BF16
+    lo = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
+    hi = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true));
+#else
+    lo = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false));
+    hi = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true));
+#endif
+}
+
+// sum over the LPR (8 or 4) consecutive lanes that hold one byte row, result in every lane of the group
+template <int LPR>
+__device__ __forceinline__ float byte_row_sum(float x) {
+    if (LPR == 8) x = dpp_add<0x141>(x);                                   // row_half_mirror (8 lanes: i <-> 7-i)
+    x = dpp_add<0x4E>(x);                                                  // quad_perm [2,3,0,1]
+    x = dpp_add<0xB1>(x);                                                  // quad_perm [1,0,3,2]
+    return x;
+}
+// sum / max over the 64/LPR row-group slots of the wave (lanes with equal lane % LPR), result in every lane
+template <int LPR>
+__device__ __forceinline__ float slots_sum(float x) {
+    if (LPR == 4) x = dpp_add<0x124>(x);                                   // row_ror:4 inside the 16-lane row
+    x = dpp_add<0x128>(x);                                                 // row_ror:8
+    return xor32_partner_sum(xor16_partner_sum(x));
+}
+template <int LPR>
+__device__ __forceinline__ float slots_max(float x) {
+    if (LPR == 4) x = dpp_max<0x124>(x);
+    x = dpp_max<0x128>(x);
+    return xor32_partner_max(xor16_partner_max(x));
+}
+
+// One workgroup of WAVES waves owns (query t, kv head g, partition).  The partition is cut into chunks of U row groups (TPI = U * RPI
+// consecutive tokens); in a FULL round every wave takes one whole chunk (chunk r * WAVES + wave) and requests its U groups of K and of V
+// with no validity tests; what is left after the last full round is dealt out group by group (group j -> wave j % WAVES) and requested
+// AHEAD of the last full round's arithmetic.  UB: block_size (and the partition size) is a multiple of TPI, so a chunk lies inside one
+// cache block: its block-table entry is a scalar read (v_readlane) from a register copy of 64 entries, and a row address is scalar base +
+// lane offset.  Otherwise every lane looks its row's block up.  num_parts == 1: the workgroup writes the 16-bit rows itself;
+// else f32 partials in the layout of attn_workspace_bytes, merged by attn_fp8_merge_kernel.
+template <int D, int G, int U, int WAVES, bool UB>
+__global__ __launch_bounds__(WAVES * 64) void attn_fp8_kernel(AttnFp8Params p) {
+    constexpr int LPR = D / 16;         // lanes per byte row
+    constexpr int RPI = 64 / LPR;       // rows per wave-instruction (= tokens per row group)
+    constexpr int TPI = RPI * U;        // tokens per chunk
+    const int part = blockIdx.x % p.num_parts, g = (blockIdx.x / p.num_parts) % p.KVH;
+    const int t = blockIdx.x / (p.num_parts * p.KVH);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int dc = lane % LPR, tg = lane / LPR;
+    const int p0 = part * p.part_size;
+    const bool direct = p.num_parts == 1;
+
+    const int32_t *bt = p.block_tables + (int64_t)t * p.max_blocks;
+    int bt_chunk = -1, bt_reg = 0;                   // UB: register copy of 64 block-table entries (lane j holds entry 64 * c + j)
+    auto load_bt_chunk = [&](int c) {
+        bt_chunk = c;
+        const int idx = (c << 6) + lane;
+        bt_reg = idx < p.max_blocks ? bt[idx] : 0;
+    };
+    if (UB) load_bt_chunk((p.bs_shift >= 0 ? p0 >> p.bs_shift : p0 / p.block_size) >> 6);   // requested with ctx and q, ahead of their use
+
+    // q slice of this lane (16 elements) for the G heads of kv head g, as 16-bit pairs for v_dot2
+    half2_t qv[G][8];
+    {
+        const half_t *qrow = p.q + (int64_t)t * p.ldq + (int64_t)g * G * D + dc * 16;
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const half8_t a = *reinterpret_cast<const half8_t *>(qrow + i * D), b = *reinterpret_cast<const half8_t *>(qrow + i * D + 8);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { qv[i][j] = (half2_t){a[2 * j], a[2 * j + 1]}; qv[i][4 + j] = (half2_t){b[2 * j], b[2 * j + 1]}; }
+        }
+    }
+    const int ctx = p.ctx_lens[t];
+    if (p0 >= ctx && !direct) return;                // empty partition: the merge skips it too
+    const int pend = max(p0, min(ctx, p0 + p.part_size));
+    const int row_bytes = p.KVH * D;
+
+    // byte offset of (scalar token tb, kv head g, d = 0) through the register copy of the block table
+    auto block_base = [&](int tb) -> int64_t {
+        int bi, bo;
+        if (p.bs_shift >= 0) { bi = tb >> p.bs_shift; bo = tb & (p.block_size - 1); }
+        else { bi = tb / p.block_size; bo = tb - bi * p.block_size; }
+        if ((bi >> 6) != bt_chunk) load_bt_chunk(bi >> 6);
+        const int blk = __builtin_amdgcn_readlane(bt_reg, bi & 63);
+        return (((int64_t)blk * p.block_size + bo) * p.KVH + g) * D;
+    };
+    // per-lane form (block sizes that are no multiple of the chunk)
+    auto lane_row = [&](int tok) -> int64_t {
+        int bi, bo;
+        if (p.bs_shift >= 0) { bi = tok >> p.bs_shift; bo = tok & (p.block_size - 1); }
+        else { bi = tok / p.block_size; bo = tok - bi * p.block_size; }
+        return (((int64_t)bt[bi] * p.block_size + bo) * p.KVH + g) * D + dc * 16;
+    };
+    auto load16 = [](const uint8_t *ptr) { return __builtin_nontemporal_load(reinterpret_cast<const uint4_t *>(ptr)); };
+
+    // online softmax state per head AND per row-group slot of the wave (merged once at the end)
+    float m[G], l[G], acc[G][16];
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        m[i] = -INFINITY; l[i] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[i][j] = 0.f;
+    }
+
+    // scores, online softmax and p.v for U row groups; CHECK: slot u holds token tok0 + u * WAVES * RPI + tg, valid < pend
+    auto process = [&](auto check, const uint4_t (&kk)[U], const uint4_t (&vv)[U], int tok0) {
+        constexpr bool CHECK = decltype(check)::value;
+        float s[U][G];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const bool valid = !CHECK || tok0 + u * (WAVES * RPI) + tg < pend;
+            half2_t kh[8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) fp8x4_to_half2(kk[u][j], kh[2 * j], kh[2 * j + 1]);
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                float d = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) d = dot2(kh[j], qv[i][j], d);
+                d = byte_row_sum<LPR>(d);
+                s[u][i] = valid ? d * p.scale : -INFINITY;               // (a NaN byte behind the context ends here)
+            }
+        }
+        float alpha[G], ms[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            float mx = s[0][i];
+#pragma unroll
+            for (int u = 1; u < U; ++u) mx = fmaxf(mx, s[u][i]);
+            const float mn = fmaxf(m[i], mx);
+            ms[i] = (CHECK && mn == -INFINITY) ? 0.f : mn;               // a slot that has seen no valid token yet
+            alpha[i] = __expf(m[i] - ms[i]);                             // m = -inf on first use -> 0
+            m[i] = mn;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[i][j] *= alpha[i];
+        }
+        float ps[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) ps[i] = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            // the row's V bytes once for all G heads (rows behind the context are never requested: the remainder repeats row pend - 1 with p = 0)
+            float vf[16];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float2_t a = __builtin_amdgcn_cvt_pk_f32_fp8(vv[u][j], false), b = __builtin_amdgcn_cvt_pk_f32_fp8(vv[u][j], true);
+                vf[4 * j] = a[0]; vf[4 * j + 1] = a[1]; vf[4 * j + 2] = b[0]; vf[4 * j + 3] = b[1];
+            }
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const float pr = __expf(s[u][i] - ms[i]);
+                ps[i] += pr;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[i][j] = fmaf(pr, vf[j], acc[i][j]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < G; ++i) l[i] = __fmaf_rn(l[i], alpha[i], ps[i]);
+    };
+
+    const int ng = (pend - p0 + RPI - 1) / RPI;      // row groups of this partition, the last one possibly partial
+    const int R = (pend - p0) / (TPI * WAVES);       // full rounds: every wave gets a complete chunk
+    const int gt0 = R * (WAVES * U) + wave;          // this wave's remainder groups: gt0, gt0 + WAVES, ..
+    auto issue_remainder = [&](uint4_t (&kt)[U], uint4_t (&vt)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int gt = gt0 + u * WAVES;
+            if (gt < ng) {                           // uniform
+                const int tb = p0 + gt * RPI;        // (rows past the end repeat row pend - 1: inside the cache, masked by CHECK)
+                if (UB) {
+                    const int64_t base = block_base(tb);
+                    const unsigned lo = (unsigned)(min(tg, pend - 1 - tb) * row_bytes + dc * 16);
+                    kt[u] = load16(p.k + base + lo); vt[u] = load16(p.v + base + lo);
+                } else {
+                    const int64_t off = lane_row(min(tb + tg, pend - 1));
+                    kt[u] = load16(p.k + off); vt[u] = load16(p.v + off);
+                }
+            } else {
+                kt[u] = (uint4_t){0u, 0u, 0u, 0u}; vt[u] = (uint4_t){0u, 0u, 0u, 0u};
+            }
+        }
+    };
+
+    uint4_t kt[U], vt[U];
+    if (R == 0) issue_remainder(kt, vt);
+    for (int r = 0; r < R; ++r) {
+        const int tb = p0 + (r * WAVES + wave) * TPI;
+        uint4_t kk[U], vv[U];
+        if (UB) {
+            const int64_t base = block_base(tb);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned lo = (unsigned)((u * RPI + tg) * row_bytes + dc * 16);
+                kk[u] = load16(p.k + base + lo); vv[u] = load16(p.v + base + lo);
+            }
+        } else {
+            int64_t off[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) off[u] = lane_row(tb + u * RPI + tg);
+#pragma unroll
+            for (int u = 0; u < U; ++u) { kk[u] = load16(p.k + off[u]); vv[u] = load16(p.v + off[u]); }
+        }
+        if (r == R - 1) issue_remainder(kt, vt);
+        process(std::false_type{}, kk, vv, 0);
+    }
+    if (gt0 < ng) process(std::true_type{}, kt, vt, p0 + gt0 * RPI);
+
+    // bring the row-group slots of the wave to their common max and sum them, then merge the waves through LDS
+    __shared__ float sm_acc[WAVES][G][D];
+    __shared__ float sm_ml[WAVES][G][2];
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        const float M = slots_max<LPR>(m[i]);
+        const float w = (m[i] == -INFINITY) ? 0.f : __expf(m[i] - M);
+        l[i] = slots_sum<LPR>(l[i] * w);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[i][j] = slots_sum<LPR>(acc[i][j] * w);
+        if (tg == 0) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) sm_acc[wave][i][dc * 16 + j] = acc[i][j];
+            if (dc == 0) { sm_ml[wave][i][0] = M; sm_ml[wave][i][1] = l[i]; }
+        }
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < G * D; idx += WAVES * 64) {
+        const int i = idx / D, d = idx % D;
+        float M = sm_ml[0][i][0];
+#pragma unroll
+        for (int w2 = 1; w2 < WAVES; ++w2) M = fmaxf(M, sm_ml[w2][i][0]);
+        float o = 0.f, L = 0.f;
+#pragma unroll
+        for (int w2 = 0; w2 < WAVES; ++w2) {
+            const float mw = sm_ml[w2][i][0];
+            const float wgt = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+            o = fmaf(wgt, sm_acc[w2][i][d], o);
+            L = fmaf(wgt, sm_ml[w2][i][1], L);
+        }
+        o *= p.v_scale;                              // once per (query, head, partition): the merge of the partials is linear in o
+        const int64_t row = (int64_t)t * p.H + g * G + i;
+        if (direct) {
+            p.out[row * D + d] = (half_t)(L > 0.f ? o / L : 0.f);
+        } else {
+            const int64_t slot = row * p.num_parts + part;
+            p.part_o[slot * D + d] = o;
+            if (d == 0) { p.part_ml[slot * 2] = M; p.part_ml[slot * 2 + 1] = L; }
+        }
+    }
+}
+
+// merge of the split-KV partials (merge_partitions: attn_merge.h; v_scale is already in them): D/4 threads per (query, head)
+template <int D>
+__global__ __launch_bounds__(256) void attn_fp8_merge_kernel(const float *__restrict__ part_o, const float *__restrict__ part_ml,
+                                                             const int32_t *__restrict__ ctx_lens, int H, int part_size, int num_parts, int64_t pairs,
+                                                             half_t *__restrict__ out) {
+    constexpr int TPP = D / 4;
+    const int64_t pair = (int64_t)blockIdx.x * (256 / TPP) + threadIdx.x / TPP;
+    if (pair >= pairs) return;
+    const int t = (int)(pair / H), d = (threadIdx.x % TPP) * 4;
+    const int np = min(num_parts, (ctx_lens[t] + part_size - 1) / part_size);
+    const int64_t base = pair * num_parts;
+    const half4_t hv = merge_partitions(np,
+        [&](int i) { return *reinterpret_cast<const float2_t *>(part_ml + (base + i) * 2); },
+        [&](int i) { return *reinterpret_cast<const float4_t *>(part_o + (base + i) * D + d); });
+    *reinterpret_cast<half4_t *>(out + pair * D + d) = hv;
+}
+
+template <int D, int G, int WAVES>
+static void launch_fp8_cfg(const AttnFp8Params &p, int64_t nwg, hipStream_t s) {
+    constexpr int U = 2, TPI = 64 / (D / 16) * U;                        // 2 KiB of K and of V in flight per wave: 16 tokens at D = 128, 32 at D = 64
+    const bool ub = p.block_size % TPI == 0 && (p.num_parts == 1 || p.part_size % TPI == 0);
+    dim3 grid((unsigned)nwg), block(WAVES * 64);
+    if (ub) attn_fp8_kernel<D, G, U, WAVES, true><<<grid, block, 0, s>>>(p);
+    else attn_fp8_kernel<D, G, U, WAVES, false><<<grid, block, 0, s>>>(p);
+}
+
+template <int D, int G>
+static int launch_attn_fp8(const AttnFp8Args &a, hipStream_t s) {
+    AttnFp8Params p{};
+    p.q = (const half_t *)a.q; p.ldq = a.ldq; p.k = a.k; p.v = a.v; p.ctx_lens = a.ctx_lens; p.block_tables = a.block_tables;
+    p.max_blocks = a.max_blocks; p.block_size = a.block_size;
+    p.bs_shift = (a.block_size & (a.block_size - 1)) == 0 ? __builtin_ctz(a.block_size) : -1;
+    p.H = a.H; p.KVH = a.KVH; p.scale = a.scale * a.k_scale; p.v_scale = a.v_scale; p.out = (half_t *)a.out;
+    // Workgroups: the 16-bit kernel's rule (attention.hip, measured there): eight waves per (query, kv head) when ~256 such workgroups can be
+    // given >= 64 keys each, the context cut into 64-key-granular partitions only to reach ~256 workgroups; fewer pairs: four waves and ~1024
+    // workgroups; >= 2048 pairs of short contexts: two waves (a workgroup's life is mostly start-up and the cross-wave merge otherwise).
+    const int64_t mc = a.max_ctx > 0 ? a.max_ctx : 1, pairs = (int64_t)a.nq * a.KVH, units = (mc + 63) / 64;
+    const int waves = !a.workspace ? 4 : (pairs >= 2048 && mc <= 512) ? 2 : pairs * units >= 256 ? 8 : 4;
+    int64_t want = 1;
+    if (a.workspace && waves == 8) want = pairs >= 192 ? 1 : (256 + pairs - 1) / pairs;
+    else if (a.workspace && waves == 4) want = (1024 + pairs - 1) / pairs;
+    want = std::max<int64_t>(1, std::min(want, units));
+    const int64_t ps = ((mc + want - 1) / want + 63) / 64 * 64;
+    const int np = (int)((mc + ps - 1) / ps);
+    if (np > 1) {
+        const size_t need = (size_t)a.nq * a.H * np * (D + 2) * sizeof(float);
+        if (a.workspace_bytes && need > a.workspace_bytes)
+            return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: %d partitions of %d queries x %d heads need %zu workspace bytes, %zu given", np, a.nq, a.H, need,
+                             a.workspace_bytes);
+        p.part_size = (int)ps; p.num_parts = np;
+        p.part_o = (float *)a.workspace; p.part_ml = p.part_o + (int64_t)a.nq * a.H * np * D;
+    } else { p.part_size = 0x3fffffff; p.num_parts = 1; }
+    const int64_t nwg = (int64_t)p.num_parts * a.KVH * a.nq;
+    if (waves == 8) launch_fp8_cfg<D, G, 8>(p, nwg, s);
+    else if (waves == 4) launch_fp8_cfg<D, G, 4>(p, nwg, s);
+    else launch_fp8_cfg<D, G, 2>(p, nwg, s);
+    if (np > 1) {
+        const int64_t rows = (int64_t)a.H * a.nq;
+        attn_fp8_merge_kernel<D><<<dim3((unsigned)((rows + 256 / (D / 4) - 1) / (256 / (D / 4)))), dim3(256), 0, s>>>(p.part_o, p.part_ml, a.ctx_lens, a.H, p.part_size,
+                                                                                                                   np, rows, p.out);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "attention_fp8 launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int attention_fp8(const AttnFp8Args &a, hipStream_t s) {
+    if (a.nq == 0) return 0;
+    if (a.KVH <= 0 || a.H % a.KVH) return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: H=%d not a multiple of KVH=%d", a.H, a.KVH);
+    if (a.shared_len > 0 || a.balance_hint > 0)
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: the shared-prefix pass and the work-balanced form exist for 16-bit caches only");
+    if (!(a.k_scale > 0.f) || !(a.v_scale > 0.f)) return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: scales %g / %g (positive)", a.k_scale, a.v_scale);
+    const int G = a.H / a.KVH;
+    const bool shape_ok = (a.D == 64 || a.D == 128) && (G == 1 || G == 2 || G == 4);
+    if (!shape_ok || a.block_size < 64 / (a.D / 16))                    // a block holds at least one row group (8 rows at D = 128, 16 at D = 64)
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: unsupported head_dim=%d / group=%d / block_size=%d (D in {64,128}, G in {1,2,4}, block_size >= %d)",
+                         a.D, G, a.block_size, shape_ok ? 64 / (a.D / 16) : 8);
+#define NVR_ATTN8_CASE(DD, GG) if (a.D == DD && G == GG) return launch_attn_fp8<DD, GG>(a, s);
+    NVR_ATTN8_CASE(128, 1) NVR_ATTN8_CASE(128, 2) NVR_ATTN8_CASE(128, 4) NVR_ATTN8_CASE(64, 1) NVR_ATTN8_CASE(64, 2) NVR_ATTN8_CASE(64, 4)
+#undef NVR_ATTN8_CASE
+    return NVR_ERR_UNSUPPORTED;
+}
+
+}}  // namespace nvr::k / nvr::kb (NVR_DT_NS)

@@ -123,6 +123,12 @@ int gemm256_qkv_rope_store(const half_bits *x, int64_t ldx, const half_bits *W, 
 size_t attn_workspace_bytes(int64_t nq, int64_t H, int64_t D, int64_t max_ctx);
 int attention(const AttnArgs &a, bool paged, hipStream_t s);
 
+// FP8 (e4m3) KV cache: rows of the roped K and V columns of qkv [T, (H+2KVH)D] -> byte caches at slots (< 0 skips), byte = e4m3(x / scale), round to
+// nearest even, clamped to +-448; paged decode attention over such caches (D in {64,128}, H/KVH in {1,2,4}; workspace as for attention)
+int kv_store_fp8(const half_bits *qkv, const int32_t *slots, int64_t T, int64_t H, int64_t KVH, int64_t D, float k_scale, float v_scale,
+                 uint8_t *k_cache, uint8_t *v_cache, hipStream_t s);
+int attention_fp8(const AttnFp8Args &a, hipStream_t s);
+
 bool flash_prefill_ok(int D, int H, int KVH);
 int flash_tile_positions(int H, int KVH);
 int flash_prefill(const FlashArgs &a, bool paged, hipStream_t s);

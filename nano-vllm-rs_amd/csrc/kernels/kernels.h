@@ -48,6 +48,20 @@ struct AttnArgs {
     int32_t balance_hint;
 };
 
+// Paged decode attention over an FP8 (OCP e4m3fn) KV cache (kernels/attention_fp8.hip): caches [NB, bs, KVH, D] bytes, value = byte * scale
+struct AttnFp8Args {
+    const half_bits *q; int64_t ldq;          // q[t] at q + t*ldq, heads contiguous [H, D]
+    const uint8_t *k, *v;
+    const int32_t *ctx_lens;                   // [nq] keys visible to query t
+    const int32_t *block_tables; int32_t max_blocks; int32_t block_size;
+    int32_t nq, H, KVH, D;
+    float scale, k_scale, v_scale;
+    int32_t max_ctx;                           // upper bound of ctx_lens (grid sizing)
+    half_bits *out;                            // [nq, H, D] of the build's 16-bit type
+    void *workspace; size_t workspace_bytes;   // split-KV partials (attn_workspace_bytes; bytes 0 = not checked)
+    int32_t shared_len, balance_hint;          // AttnArgs' shared-prefix pass / work-balanced form: not built for byte caches (> 0: NVR_ERR_UNSUPPORTED)
+};
+
 // MFMA flash prefill attention.  A tile = up to 64/G consecutive query positions of one sequence.
 struct FlashTile { int32_t q_row0, nq, pos0, kv_ref; };   // first q row, #queries, absolute position of the first query,
                                                           // contiguous: first key row of the sequence / paged: block-table row

@@ -46,7 +46,7 @@ nvr_model_runner::~nvr_model_runner() {
     if (lm_head_t) hipFree(lm_head_t);
     void *ptrs[] = {embed, mc.tie_word_embeddings ? nullptr : lm_head, norm, cos_t, sin_t, kv_pool, h, n, qkv, attn,
                     proj, gu, act, nlast, logits, attn_ws, slabs, in_dev, d_tok, d_maxval, d_temp, d_topk, d_topp, d_keys,
-                    sample_ws, d_gather_val, d_gather_idx, d_gather_logits, d_full_logits, sample_ws_full, d_lm_pval, d_lm_pidx, d_rec, d_gather_rec, f32_gather, f32_h2};
+                    sample_ws, d_gather_val, d_gather_idx, d_gather_logits, d_full_logits, sample_ws_full, d_lm_pval, d_lm_pidx, d_rec, d_gather_rec, f32_gather, f32_h2, no_slots};
     for (void *p : ptrs) if (p) hipFree(p);
     if (in_host) hipHostFree(in_host);
     if (h_tok) hipHostFree(h_tok);
@@ -63,6 +63,12 @@ int nvr_model_runner::init() {                                       // ModelRun
     bf16 = std::strcmp(cfg.dtype, "bfloat16") == 0;                               // config.rs:51 (fp16 otherwise)
     f32 = std::strcmp(cfg.dtype, "float32") == 0;                                 // the reference-precision path (kernels/f32_path.hip): 4-byte storage,
     em = f32 ? 2 : 1;                                                             // every "16-bit" buffer below holds em x 2 bytes per element
+    kv_fp8 = std::strncmp(cfg.kv_cache_dtype, "fp8", 3) == 0;                     // "fp8" | "fp8_e4m3" (nvr_config_validate has seen the name)
+    kv_elem_bytes = kv_fp8 ? 1 : f32 ? 4 : 2;
+    if (kv_fp8 && f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8 needs dtype float16 or bfloat16 (the fp8 kernels quantise and read 16-bit rows)");
+    if (kv_fp8 && (!cfg.recompute_cached_prefix || cfg.enable_chunked_prefill))
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8 needs recompute_cached_prefix = 1 and enable_chunked_prefill = 0 (got %d / %d): there is no "
+                         "prefill attention over an fp8 cache, a prefill step attends to its own projections", cfg.recompute_cached_prefix, cfg.enable_chunked_prefill);
     if (f32) { tiled_weights = false; lm_fused = false; RC(nvr::kf::prepare()); }   // (decode steps of the f32 path replay a captured graph like the 16-bit ones)
     comm.bf16 = bf16;                                                              // the collectives round their sums to the same 16-bit type
     if (tp < 1 || rank >= tp) return nvr::fail(NVR_ERR_INVALID_ARG, "bad tensor parallel rank %ld of %ld", (long)rank, (long)tp);
@@ -75,6 +81,9 @@ int nvr_model_runner::init() {                                       // ModelRun
     Vl = V / tp; vocab_start = rank * Vl; if (rank == tp - 1) Vl = V - vocab_start;   // embed_head.rs:57-59
     scale = 1.0f / std::sqrt((float)D);                                           // attention.rs:45
     block_size = cfg.kvcache_block_size;
+    if (kv_fp8 && ((D != 64 && D != 128) || KVH <= 0 || H % KVH || (H / KVH != 1 && H / KVH != 2 && H / KVH != 4) || block_size < 64 / (D / 16)))
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8: head_dim %ld, %ld query heads per kv head, block size %ld (head_dim 64 or 128; 1, 2 or 4; "
+                         "at least 8 rows at head_dim 128, 16 at 64)", (long)D, (long)(KVH > 0 ? H / KVH : 0), (long)block_size);
     max_tokens = cfg.max_num_batched_tokens; max_seqs = cfg.max_num_seqs;
     max_pos = std::min<int64_t>(mc.max_position_embeddings, std::max<int64_t>(cfg.max_model_len, 1));
     max_blocks_per_seq = (max_pos + block_size - 1) / block_size + 1;
@@ -201,13 +210,18 @@ int nvr_model_runner::init() {                                       // ModelRun
         size_t free_b = 0, total_b = 0;
         NVR_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
         double budget = (double)free_b - (1.0 - cfg.gpu_memory_utilization) * (double)total_b;
-        int64_t nb = (int64_t)(budget / (double)(block_elems * 2 * em * 2 * L));
+        int64_t nb = (int64_t)(budget / (double)(block_elems * kv_elem_bytes * 2 * L));
         if (nb < 1) return nvr::fail(NVR_ERR_HIP, "not enough free HBM for one KV block");
         num_blocks = nb;
     }
     kv_layer_elems = (size_t)num_blocks * block_elems;
-    NVR_HIP_CHECK(hipMalloc((void **)&kv_pool, kv_layer_elems * 2 * L * sizeof(uint16_t) * em));
-    NVR_HIP_CHECK(hipMemsetAsync(kv_pool, 0, kv_layer_elems * 2 * L * sizeof(uint16_t) * em, stream));   // Tensor::zeros :379-389
+    NVR_HIP_CHECK(hipMalloc((void **)&kv_pool, kv_layer_elems * 2 * L * kv_elem_bytes));
+    NVR_HIP_CHECK(hipMemsetAsync(kv_pool, 0, kv_layer_elems * 2 * L * kv_elem_bytes, stream));   // Tensor::zeros :379-389
+    if (kv_fp8) {
+        const size_t ns = (size_t)std::max(max_tokens, max_seqs);
+        RC(dmalloc(&no_slots, ns));
+        NVR_HIP_CHECK(hipMemsetAsync(no_slots, 0xFF, ns * sizeof(int32_t), stream));              // every entry -1
+    }
     NVR_HIP_CHECK(hipStreamSynchronize(stream));
     return NVR_OK;
 }
@@ -834,6 +848,7 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
     if (f32) return forward_f32(T, B, is_prefill, max_ctx);
     if (is_prefill && tp_overlap == 2 && mb_rows > 0) return forward_prefill_two(T, B);
     const bool tl = tiled_weights && T <= 64;                            // decode-sized steps stream the tiled weight copies
+    const int32_t *pslots = kv_fp8 ? no_slots : slots;                   // fp8 cache: the projection launches store no cache row (kv_store_fp8 below)
     const bool embed_norm = L > 0 && KD(embedding_rmsnorm_ok(T, Hd));                    // decode-sized: K1 + the first norm in one launch
     if (embed_norm) RC(KD(embedding_rmsnorm(ids, T, embed, layers[0].ln1, mc.rms_norm_eps, Hd, h, n, st)));
     else RC(KD(embedding(ids, T, embed, Hd, h, st)));
@@ -843,12 +858,14 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
         if (mc.qk_norm || mc.use_bias) {         // A-27: the head norms sit between the projection and RoPE: plain GEMM, then one
             RC(KD(linear(n, Hd, w.qkv, T, Hd, QKV, qkv, false, st, tl ? w.qkv_t : nullptr)));      // norm + RoPE + KV-store launch
             if (mc.use_bias) RC(KD(add_bias(qkv, w.qkv_b, T, QKV, st)));                            // A-30: the bias precedes the norms and RoPE (qwen3.rs:208-222)
-            RC(KD(rope_store_kv(qkv, pos, slots, T, H, KVH, D, cos_t, sin_t, k_cache(l), v_cache(l), st, w.q_norm, w.k_norm, mc.rms_norm_eps)));
+            RC(KD(rope_store_kv(qkv, pos, pslots, T, H, KVH, D, cos_t, sin_t, k_cache(l), v_cache(l), st, w.q_norm, w.k_norm, mc.rms_norm_eps)));
         } else {
             // qkv GEMM with the RoPE + KV-store epilogue (K3..K6 in one launch)
-            RC(KD(linear_qkv_rope_store(n, Hd, w.qkv, T, Hd, H, KVH, D, pos, slots, cos_t, sin_t, qkv, k_cache(l), v_cache(l), st, tl ? w.qkv_t : nullptr,
+            RC(KD(linear_qkv_rope_store(n, Hd, w.qkv, T, Hd, H, KVH, D, pos, pslots, cos_t, sin_t, qkv, k_cache(l), v_cache(l), st, tl ? w.qkv_t : nullptr,
                                         is_prefill && n_tiles > 0 && (prefill_paged || prefill_kv_cache))));
         }
+        if (kv_fp8)                                                  // the roped K / V columns of qkv -> e4m3 bytes at the step's slots (attention.rs:150-174)
+            RC(KD(kv_store_fp8(qkv, slots, T, H, KVH, D, k_scale, v_scale, reinterpret_cast<uint8_t *>(k_cache(l)), reinterpret_cast<uint8_t *>(v_cache(l)), st)));
         k::AttnArgs a{};
         a.q = qkv; a.ldq = QKV; a.ctx_lens = ctx; a.nq = (int32_t)T; a.H = (int32_t)H; a.KVH = (int32_t)KVH; a.D = (int32_t)D;
         a.scale = scale; a.max_ctx = (int32_t)max_ctx; a.out = attn;
@@ -867,6 +884,13 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
         } else if (is_prefill) {                                     // head shapes outside the MFMA kernel: row kernel
             a.k = qkv + H * D; a.v = qkv + (H + KVH) * D; a.ldkv = QKV; a.kv_base = d_kvbase; a.workspace = nullptr;
             RC(KD(attention(a, false, st)));
+        } else if (kv_fp8) {                                         // flash_attention_decode, attention.rs:225-235, over the byte cache
+            k::AttnFp8Args f{};
+            f.q = qkv; f.ldq = QKV; f.k = reinterpret_cast<const uint8_t *>(k_cache(l)); f.v = reinterpret_cast<const uint8_t *>(v_cache(l));
+            f.ctx_lens = ctx; f.block_tables = bt; f.max_blocks = (int32_t)max_blocks_per_seq; f.block_size = (int32_t)block_size;
+            f.nq = (int32_t)T; f.H = (int32_t)H; f.KVH = (int32_t)KVH; f.D = (int32_t)D; f.scale = scale; f.k_scale = k_scale; f.v_scale = v_scale;
+            f.max_ctx = (int32_t)max_ctx; f.out = attn; f.workspace = attn_ws; f.workspace_bytes = attn_ws_bytes;
+            RC(KD(attention_fp8(f, st)));
         } else {                                                     // flash_attention_decode, attention.rs:225-235
             a.k = k_cache(l); a.v = v_cache(l); a.block_tables = bt; a.max_blocks = (int32_t)max_blocks_per_seq;
             a.block_size = (int32_t)block_size; a.workspace = attn_ws; a.workspace_bytes = attn_ws_bytes; a.tickets = attn_tickets;
@@ -913,6 +937,7 @@ int nvr_model_runner::execute(nvr_seq *const *seqs, size_t nseq, bool is_prefill
                          "nvr_local_group_attach); partial sums would be returned as results", (long)tp);
     if (nseq == 0) return nvr::fail(NVR_ERR_INVALID_ARG, "execute_model: empty batch");
     facts_shown_valid = false;                                           // the accessors follow this step until the engine presents another
+    stepped = true;
     if ((int64_t)nseq > max_seqs) return nvr::fail(NVR_ERR_INVALID_ARG, "execute_model: %zu sequences > max_num_seqs %ld", nseq, (long)max_seqs);
     char *hd = in_host + off_dec;
     int64_t *ids = (int64_t *)(hd + dof_ids), *pos = (int64_t *)(hd + dof_pos);
@@ -960,14 +985,14 @@ int nvr_model_runner::execute(nvr_seq *const *seqs, size_t nseq, bool is_prefill
         // the free list in order until it has been recycled) token p of a sequence sits at cache row table[0] * bs + p and the kernel runs in
         // its contiguous form (-1.7 ms of a 32 x 1024 prefill); otherwise it walks the block tables like a prefill behind a cached prefix
         // (-0.5 ms).  q/k-norm models keep the qkv buffer (their norm + RoPE launch writes both anyway).
-        prefill_kv_cache = flash_ok && !prefill_paged && !mc.qk_norm && !mc.use_bias;
+        prefill_kv_cache = flash_ok && !prefill_paged && !mc.qk_norm && !mc.use_bias && !kv_fp8;   // (an fp8 cache is never read by a prefill step)
         for (size_t b = 0; b < nseq && prefill_kv_cache; ++b) {
             const nvr_seq &sq = *seqs[b];
             const size_t nb = std::min(sq.block_table.size(), (size_t)(((int64_t)sq.len() + bs - 1) / bs));
             for (size_t j = 1; j < nb; ++j)
                 if (sq.block_table[j] != sq.block_table[j - 1] + 1) { prefill_kv_cache = false; break; }
         }
-        if (flash_ok && !prefill_paged && !mc.qk_norm && !mc.use_bias && !prefill_kv_cache) prefill_paged = true;
+        if (flash_ok && !prefill_paged && !mc.qk_norm && !mc.use_bias && !prefill_kv_cache && !kv_fp8) prefill_paged = true;
         const int qb = flash_ok ? KD(flash_tile_positions((int)H, (int)KVH)) : 1;
         {   // the step's arrays back to back at the start of the arena (sized by THIS step's token count): one upload instead of seven
             size_t o = 0;
@@ -1050,7 +1075,7 @@ int nvr_model_runner::execute(nvr_seq *const *seqs, size_t nseq, bool is_prefill
             //  step's shape — so the parts call that kernel directly; the plain graph only: see forward_prefill_two)
             {
                 const int64_t rest = total - mb_rows;
-                bool ok = tp_overlap == 2 && comm.active() && comm_stream && !mc.qk_norm && !mc.use_bias && !chunked && mb_rows >= 512 && rest >= 512;
+                bool ok = tp_overlap == 2 && comm.active() && comm_stream && !mc.qk_norm && !mc.use_bias && !chunked && !kv_fp8 && mb_rows >= 512 && rest >= 512;
                 // kinds: 0 qkv (+RoPE), 1 o_proj, 2 gate_up (+SiLU), 3 down_proj
                 const int64_t Ks[4] = {Hd, H * D, Hd, I}, Ns[4] = {QKV, Hd, 2 * I, Hd};
                 for (int kd = 0; kd < 4 && ok; ++kd) {
@@ -1085,6 +1110,7 @@ int nvr_model_runner::execute(nvr_seq *const *seqs, size_t nseq, bool is_prefill
         decode_shared_len = shared_prefix_plan(seqs, nseq, (int32_t *)(hd + dof_skv0), (int32_t *)(hd + dof_srows), (int32_t *)(hd + dof_scount),
                                                &decode_shared_rows);
         decode_ragged = ragged_batch(nseq, sum_ctx, (cfg.enforce_eager || graphs_disabled) ? max_ctx : (max_ctx + 255) / 256 * 256);
+        if (kv_fp8) { decode_shared_len = 0; decode_shared_rows = 0; decode_ragged = false; }   // attention_fp8 has neither form
     }
     // one H2D per array actually used this step (K19)
     auto up = [&](size_t off, size_t bytes) { return hipMemcpyAsync(in_dev + off, in_host + off, bytes, hipMemcpyHostToDevice, stream); };
@@ -1179,6 +1205,7 @@ int nvr_model_runner::execute_decode_ahead(nvr_seq *const *seqs, size_t nseq, in
     decode_shared_len = shared_prefix_plan(seqs, nseq, (int32_t *)(hd + dof_skv0), (int32_t *)(hd + dof_srows), (int32_t *)(hd + dof_scount),
                                            &decode_shared_rows);
     decode_ragged = ragged_batch(nseq, sum_ctx, (cfg.enforce_eager || graphs_disabled) ? max_ctx : (max_ctx + 255) / 256 * 256);
+    if (kv_fp8) { decode_shared_len = 0; decode_shared_rows = 0; decode_ragged = false; }
     NVR_HIP_CHECK(hipMemcpyAsync(in_dev + off_dec + dof_pos, hd + dof_pos, dof_bt + nseq * max_blocks_per_seq * 4 - dof_pos, hipMemcpyHostToDevice, stream));
     last_rows = nseq; last_prefill = false; last_tokens = (int64_t)nseq;
     lm_parts = KD(lm_head_parts((int64_t)nseq, Hd, Vl, Hd));

@@ -49,6 +49,13 @@ struct nvr_model_runner {
     float *cos_t = nullptr, *sin_t = nullptr;
     uint16_t *kv_pool = nullptr;
     size_t kv_layer_elems = 0;             // elements of one K (or V) cache of one layer
+    size_t kv_elem_bytes = 2;              // bytes of a cache element: 2 (fp16 / bf16), 4 (float32) or 1 (kv_fp8)
+    // nvr_config.kv_cache_dtype = "fp8": the pool holds OCP e4m3 bytes, value = byte * scale (kernels/attention_fp8.hip).  The projection launches of a
+    // step get no_slots (all -1: they store no cache row) and one kv_store_fp8 launch per layer quantises the roped K / V columns of qkv; prefill attention
+    // reads qkv, decode attention is attention_fp8.
+    bool kv_fp8 = false, stepped = false;  // stepped: a step has been executed (the scales are fixed from then on)
+    float k_scale = 1.f, v_scale = 1.f;
+    int32_t *no_slots = nullptr;           // [max(max_tokens, max_seqs)] of -1
 
     // activations
     uint16_t *h = nullptr, *n = nullptr, *qkv = nullptr, *attn = nullptr, *proj = nullptr, *gu = nullptr, *act = nullptr,
@@ -130,8 +137,9 @@ struct nvr_model_runner {
     void present_step(int parity, size_t rows);          // the logits accessors now refer to THAT step, whatever has been launched behind it
     int ensure_logits();                                 // materialise the last step's f32 logits if it skipped their stores
     int sample(nvr_seq *const *seqs, size_t nseq, int64_t *out);
-    uint16_t *k_cache(size_t l) { return kv_pool + (2 * l) * kv_layer_elems * em; }
-    uint16_t *v_cache(size_t l) { return kv_pool + (2 * l + 1) * kv_layer_elems * em; }
+    // (kv_fp8: the pool holds one byte per element and these address bytes; the 16-bit launches that receive them store nothing — no_slots)
+    uint16_t *k_cache(size_t l) { return reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(kv_pool) + (2 * l) * kv_layer_elems * kv_elem_bytes); }
+    uint16_t *v_cache(size_t l) { return reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(kv_pool) + (2 * l + 1) * kv_layer_elems * kv_elem_bytes); }
 
 private:
     int forward(int64_t T, int64_t B, bool is_prefill, int64_t max_ctx);

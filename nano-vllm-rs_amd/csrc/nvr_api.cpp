@@ -202,6 +202,15 @@ int nvr_runner_kv_cache(nvr_model_runner_t *r, size_t layer, void **kd, void **v
     *kd = r->k_cache(layer); *vd = r->v_cache(layer);
     return NVR_OK;
 }
+const char *nvr_runner_kv_cache_dtype(const nvr_model_runner_t *r) { return r->kv_fp8 ? "fp8_e4m3" : r->f32 ? "float32" : r->bf16 ? "bfloat16" : "float16"; }
+int nvr_runner_set_kv_scales(nvr_model_runner_t *r, float k_scale, float v_scale) {
+    if (!r->kv_fp8) return nvr::fail(NVR_ERR_UNSUPPORTED, "nvr_runner_set_kv_scales: the runner's KV cache is %s, not fp8", nvr_runner_kv_cache_dtype(r));
+    if (!(k_scale > 0.f) || !(v_scale > 0.f) || std::isinf(k_scale) || std::isinf(v_scale))
+        return nvr::fail(NVR_ERR_INVALID_ARG, "nvr_runner_set_kv_scales: scales %g / %g (positive, finite)", k_scale, v_scale);
+    if (r->stepped) return nvr::fail(NVR_ERR_INVARIANT, "nvr_runner_set_kv_scales: the runner has executed a step (its cache rows hold the old scales)");
+    r->k_scale = k_scale; r->v_scale = v_scale;
+    return NVR_OK;
+}
 void *nvr_runner_stream(nvr_model_runner_t *r) { return r->stream; }
 int nvr_comm_unique_id(uint8_t id_out[128]) { return nvr::Comm::unique_id(id_out); }
 int nvr_runner_replay_last_decode_graph(nvr_model_runner_t *r, int n) { NVR_GUARD_BEGIN return r->replay_last_decode_graph(n); NVR_GUARD_END(NVR_ERR_INVARIANT) }
@@ -643,6 +652,21 @@ int nvr_paged_attn_decode_shared(const nvr_half *q, int64_t ldq, const nvr_half 
     a.D = (int32_t)D; a.scale = scale; a.max_ctx = m->max_context_len; a.out = out; a.workspace = ws;
     a.shared_len = (int32_t)shared_len; a.shared_rows = rows; a.shared_kv0 = kv0; a.shared_count = count;
     return KO(attention(a, true, (hipStream_t)s));
+}
+int nvr_kv_store_fp8(const nvr_half *qkv, const int32_t *slots, int64_t T, int64_t H, int64_t KVH, int64_t D, float k_scale, float v_scale,
+                     uint8_t *kc, uint8_t *vc, void *s) {
+    if (g_ops_f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "nvr_kv_store_fp8: quantises 16-bit rows (nvr_ops_set_dtype float16 | bfloat16)");
+    return KO(kv_store_fp8(qkv, slots, T, H, KVH, D, k_scale, v_scale, kc, vc, (hipStream_t)s));
+}
+int nvr_paged_attn_decode_fp8(const nvr_half *q, int64_t ldq, const uint8_t *kc, const uint8_t *vc, const nvr_attn_meta *m, int64_t H, int64_t KVH,
+                              int64_t D, int64_t bs, float scale, float k_scale, float v_scale, nvr_half *out, void *ws, uint32_t *tickets, void *s) {
+    if (g_ops_f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "nvr_paged_attn_decode_fp8: 16-bit queries and outputs (nvr_ops_set_dtype float16 | bfloat16)");
+    (void)tickets;
+    k::AttnFp8Args a{};
+    a.q = q; a.ldq = ldq; a.k = kc; a.v = vc; a.ctx_lens = m->context_lens; a.block_tables = m->block_tables; a.max_blocks = m->max_blocks;
+    a.block_size = (int32_t)bs; a.nq = m->batch; a.H = (int32_t)H; a.KVH = (int32_t)KVH; a.D = (int32_t)D; a.scale = scale; a.k_scale = k_scale;
+    a.v_scale = v_scale; a.max_ctx = m->max_context_len; a.out = out; a.workspace = ws;
+    return KO(attention_fp8(a, (hipStream_t)s));
 }
 // host-side tile list for the flash kernels from cu_seqlens_q (+ context lens for the paged variant)
 static int run_prefill_attn(const nvr_half *q, int64_t ldq, const nvr_half *kk, const nvr_half *v, int64_t ldkv, const nvr_attn_meta *m,
