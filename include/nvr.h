@@ -129,10 +129,13 @@ typedef struct nvr_config {
                                           has the runner's dtype; "fp8" | "fp8_e4m3": the cache holds OCP e4m3 bytes (half the K/V bytes per decode step,
                                           twice the blocks per HBM budget with num_kvcache_blocks = -2), value = byte * scale with one k_scale and one
                                           v_scale per runner (nvr_runner_set_kv_scales, default 1.0).  Such a runner writes the cache with nvr_kv_store_fp8,
-                                          decodes with nvr_paged_attn_decode_fp8, and its prefill attention reads K/V from the step's own projections: it
-                                          needs recompute_cached_prefix = 1, enable_chunked_prefill = 0 and a 16-bit dtype, head_dim 64 / 128 and 1, 2 or 4
-                                          query heads per kv head (NVR_ERR_UNSUPPORTED otherwise); it never takes the shared-prefix or the work-balanced
-                                          decode launch.  Anything else: NVR_ERR_INVALID_ARG ("Unsupported kv_cache_dtype: ...") */
+                                          decodes with nvr_paged_attn_decode_fp8; a prefill step of whole prompts attends to the step's own 16-bit
+                                          projections, a step behind a cached prefix or of a later chunk reads EVERY key, its own rows included, from the
+                                          bytes (nvr_attn_prefill_paged_fp8) — so a prompt served behind a cached prefix or in chunks sees quantised K/V
+                                          where the same prompt served whole sees its projections; decode always sees the bytes.  It needs a 16-bit dtype,
+                                          head_dim 64 / 128 and 1, 2 or 4 query heads per kv head, and for recompute_cached_prefix = 0 or
+                                          enable_chunked_prefill = 1 a kvcache_block_size that is a power of two >= 64 (NVR_ERR_UNSUPPORTED otherwise); it
+                                          never takes the shared-prefix or the work-balanced decode launch.  Anything else: NVR_ERR_INVALID_ARG ("Unsupported kv_cache_dtype: ...") */
 } nvr_config;
 NVR_API void nvr_config_default(nvr_config *cfg);                    /* config.rs:54-71 */
 NVR_API int nvr_config_validate(const nvr_config *cfg);              /* config.rs:83-119 */
@@ -615,6 +618,13 @@ NVR_API int nvr_attn_prefill_varlen(const nvr_half *q, const nvr_half *k, const 
 NVR_API int nvr_attn_prefill_paged(const nvr_half *q, int64_t ldq, const nvr_half *k_cache, const nvr_half *v_cache,
                                    const nvr_attn_meta *meta, int64_t T, int64_t H, int64_t KVH, int64_t D, int64_t block_size,
                                    float scale, nvr_half *out, void *stream);
+/* K8 over an FP8 (e4m3) cache: the semantics of nvr_attn_prefill_paged with K = k_scale * bytes, V = v_scale * bytes (caches [NB, bs, KVH, D]
+ * bytes as nvr_kv_store_fp8 writes them; k_scale is folded into the softmax scale, v_scale multiplies the finished row; Q is not quantised).
+ * Keys at or beyond a context's length never contribute, whatever their bytes, and block-table entries past the context are not read.
+ * D in {64, 128}, H / KVH in {1, 2, 4}, block_size a power of two and a multiple of 64; other shapes and "float32": NVR_ERR_UNSUPPORTED */
+NVR_API int nvr_attn_prefill_paged_fp8(const nvr_half *q, int64_t ldq, const uint8_t *k_cache, const uint8_t *v_cache,
+                                       const nvr_attn_meta *meta, int64_t T, int64_t H, int64_t KVH, int64_t D, int64_t block_size,
+                                       float scale, float k_scale, float v_scale, nvr_half *out, void *stream);
 /* K13 SiluAndMul, activation.rs:46-63: [T,2I] -> [T,I] */
 NVR_API int nvr_silu_and_mul(const nvr_half *x, int64_t T, int64_t I, nvr_half *out, void *stream);
 /* The rest of src/layers/activation.rs (r06; not on the Qwen3 path, which uses SiluAndMul only): ActivationType (:111-117), its FromStr (:169-182) and

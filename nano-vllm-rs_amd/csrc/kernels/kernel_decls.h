@@ -136,6 +136,9 @@ int flash_shared_prefix(const half_bits *q, int64_t ldq, const half_bits *k_cach
                         int32_t max_blocks, int32_t block_size, int32_t nq, int32_t H, int32_t KVH, int32_t D, float scale,
                         int32_t part_len, int32_t sparts, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s,
                         const int32_t *rows = nullptr, const int32_t *count = nullptr);
+// paged flash prefill over byte caches: D in {64,128}, H/KVH in {1,2,4}, block_size a power of two and a multiple of the 64-key step
+bool flash_prefill_fp8_ok(int D, int H, int KVH, int block_size);
+int flash_prefill_fp8(const FlashFp8Args &a, hipStream_t s);
 
 // sampler (top-k / top-p / gumbel)
 size_t sample_workspace_bytes(int64_t B, int64_t V);

@@ -74,6 +74,17 @@ struct FlashArgs {
     half_bits *out;                                        // [rows, H, D]
 };
 
+// MFMA flash prefill attention over an FP8 (e4m3) KV cache through the block tables (kernels/flash_prefill_fp8.hip): FlashArgs' paged form
+// with byte caches, value = byte * scale; tiles as for flash_prefill (flash_tile_positions)
+struct FlashFp8Args {
+    const half_bits *q; int64_t ldq;
+    const uint8_t *k, *v;                                  // caches [NB, bs, KVH, D] bytes
+    const int32_t *block_tables; int32_t max_blocks, block_size;
+    const FlashTile *tiles; int32_t ntiles;                // device array; kv_ref = block-table row
+    int32_t H, KVH, D; float scale, k_scale, v_scale;
+    half_bits *out;                                        // [rows, H, D] of the build's 16-bit type
+};
+
 // Config.dtype = "float32": attention arguments of the f32 path (kernels/f32_path.hip)
 struct AttnArgsF {
     const float *q; int64_t ldq;

@@ -66,9 +66,6 @@ int nvr_model_runner::init() {                                       // ModelRun
     kv_fp8 = std::strncmp(cfg.kv_cache_dtype, "fp8", 3) == 0;                     // "fp8" | "fp8_e4m3" (nvr_config_validate has seen the name)
     kv_elem_bytes = kv_fp8 ? 1 : f32 ? 4 : 2;
     if (kv_fp8 && f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8 needs dtype float16 or bfloat16 (the fp8 kernels quantise and read 16-bit rows)");
-    if (kv_fp8 && (!cfg.recompute_cached_prefix || cfg.enable_chunked_prefill))
-        return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8 needs recompute_cached_prefix = 1 and enable_chunked_prefill = 0 (got %d / %d): there is no "
-                         "prefill attention over an fp8 cache, a prefill step attends to its own projections", cfg.recompute_cached_prefix, cfg.enable_chunked_prefill);
     if (f32) { tiled_weights = false; lm_fused = false; RC(nvr::kf::prepare()); }   // (decode steps of the f32 path replay a captured graph like the 16-bit ones)
     comm.bf16 = bf16;                                                              // the collectives round their sums to the same 16-bit type
     if (tp < 1 || rank >= tp) return nvr::fail(NVR_ERR_INVALID_ARG, "bad tensor parallel rank %ld of %ld", (long)rank, (long)tp);
@@ -84,6 +81,11 @@ int nvr_model_runner::init() {                                       // ModelRun
     if (kv_fp8 && ((D != 64 && D != 128) || KVH <= 0 || H % KVH || (H / KVH != 1 && H / KVH != 2 && H / KVH != 4) || block_size < 64 / (D / 16)))
         return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8: head_dim %ld, %ld query heads per kv head, block size %ld (head_dim 64 or 128; 1, 2 or 4; "
                          "at least 8 rows at head_dim 128, 16 at 64)", (long)D, (long)(KVH > 0 ? H / KVH : 0), (long)block_size);
+    // a prefill step behind a cached prefix or of a later chunk reads the byte cache through the block tables (kernels/flash_prefill_fp8.hip)
+    if (kv_fp8 && (!cfg.recompute_cached_prefix || cfg.enable_chunked_prefill) && !KD(flash_prefill_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size)))
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8 with recompute_cached_prefix = 0 or enable_chunked_prefill = 1 (got %d / %d) needs a "
+                         "kvcache_block_size that is a power of two >= 64 (got %ld): the paged prefill attention over an fp8 cache takes its 64-key steps from "
+                         "inside one block", cfg.recompute_cached_prefix, cfg.enable_chunked_prefill, (long)block_size);
     max_tokens = cfg.max_num_batched_tokens; max_seqs = cfg.max_num_seqs;
     max_pos = std::min<int64_t>(mc.max_position_embeddings, std::max<int64_t>(cfg.max_model_len, 1));
     max_blocks_per_seq = (max_pos + block_size - 1) / block_size + 1;
@@ -862,14 +864,21 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
         } else {
             // qkv GEMM with the RoPE + KV-store epilogue (K3..K6 in one launch)
             RC(KD(linear_qkv_rope_store(n, Hd, w.qkv, T, Hd, H, KVH, D, pos, pslots, cos_t, sin_t, qkv, k_cache(l), v_cache(l), st, tl ? w.qkv_t : nullptr,
-                                        is_prefill && n_tiles > 0 && (prefill_paged || prefill_kv_cache))));
+                                        is_prefill && n_tiles > 0 && (prefill_paged || prefill_kv_cache) && !kv_fp8)));   // (kv_store_fp8 reads the k / v columns)
         }
         if (kv_fp8)                                                  // the roped K / V columns of qkv -> e4m3 bytes at the step's slots (attention.rs:150-174)
             RC(KD(kv_store_fp8(qkv, slots, T, H, KVH, D, k_scale, v_scale, reinterpret_cast<uint8_t *>(k_cache(l)), reinterpret_cast<uint8_t *>(v_cache(l)), st)));
         k::AttnArgs a{};
         a.q = qkv; a.ldq = QKV; a.ctx_lens = ctx; a.nq = (int32_t)T; a.H = (int32_t)H; a.KVH = (int32_t)KVH; a.D = (int32_t)D;
         a.scale = scale; a.max_ctx = (int32_t)max_ctx; a.out = attn;
-        if (is_prefill && n_tiles > 0) {                             // flash_attention_varlen, attention.rs:177-208 (MFMA)
+        if (is_prefill && n_tiles > 0 && kv_fp8 && prefill_paged) {  // cached prefixes / later chunks over the byte cache: EVERY key, the step's own rows
+            k::FlashFp8Args f{};                                     // included, comes from the bytes kv_store_fp8 has just written (K8)
+            f.q = qkv; f.ldq = QKV; f.k = reinterpret_cast<const uint8_t *>(k_cache(l)); f.v = reinterpret_cast<const uint8_t *>(v_cache(l));
+            f.block_tables = dd_bt; f.max_blocks = (int32_t)max_blocks_per_seq; f.block_size = (int32_t)block_size;
+            f.tiles = (const k::FlashTile *)(in_dev + off_tiles); f.ntiles = (int32_t)n_tiles;
+            f.H = (int32_t)H; f.KVH = (int32_t)KVH; f.D = (int32_t)D; f.scale = scale; f.k_scale = k_scale; f.v_scale = v_scale; f.out = attn;
+            RC(KD(flash_prefill_fp8(f, st)));
+        } else if (is_prefill && n_tiles > 0) {                      // flash_attention_varlen, attention.rs:177-208 (MFMA)
             k::FlashArgs f{};
             f.q = qkv; f.ldq = QKV;
             if (prefill_paged) {                                     // cached prefixes: K/V through the block tables (K8)
@@ -985,7 +994,7 @@ int nvr_model_runner::execute(nvr_seq *const *seqs, size_t nseq, bool is_prefill
         // the free list in order until it has been recycled) token p of a sequence sits at cache row table[0] * bs + p and the kernel runs in
         // its contiguous form (-1.7 ms of a 32 x 1024 prefill); otherwise it walks the block tables like a prefill behind a cached prefix
         // (-0.5 ms).  q/k-norm models keep the qkv buffer (their norm + RoPE launch writes both anyway).
-        prefill_kv_cache = flash_ok && !prefill_paged && !mc.qk_norm && !mc.use_bias && !kv_fp8;   // (an fp8 cache is never read by a prefill step)
+        prefill_kv_cache = flash_ok && !prefill_paged && !mc.qk_norm && !mc.use_bias && !kv_fp8;   // (a whole-prompt step of an fp8 runner attends to its own projections)
         for (size_t b = 0; b < nseq && prefill_kv_cache; ++b) {
             const nvr_seq &sq = *seqs[b];
             const size_t nb = std::min(sq.block_table.size(), (size_t)(((int64_t)sq.len() + bs - 1) / bs));

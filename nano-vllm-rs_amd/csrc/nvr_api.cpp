@@ -669,8 +669,13 @@ int nvr_paged_attn_decode_fp8(const nvr_half *q, int64_t ldq, const uint8_t *kc,
     return KO(attention_fp8(a, (hipStream_t)s));
 }
 // host-side tile list for the flash kernels from cu_seqlens_q (+ context lens for the paged variant)
-static int run_prefill_attn(const nvr_half *q, int64_t ldq, const nvr_half *kk, const nvr_half *v, int64_t ldkv, const nvr_attn_meta *m,
-                            bool paged, int64_t bs, int64_t T, int64_t H, int64_t KVH, int64_t D, float scale, nvr_half *out, hipStream_t st) {
+// (kv_scales: null, or {k_scale, v_scale} of byte caches behind kk / v — the paged fp8 kernel, which has no row-kernel counterpart)
+static int run_prefill_attn(const nvr_half *q, int64_t ldq, const void *kk, const void *v, int64_t ldkv, const nvr_attn_meta *m,
+                            bool paged, int64_t bs, int64_t T, int64_t H, int64_t KVH, int64_t D, float scale, nvr_half *out, hipStream_t st,
+                            const float *kv_scales = nullptr) {
+    if (kv_scales && (g_ops_f32 || !k::flash_prefill_fp8_ok((int)D, (int)H, (int)KVH, (int)bs)))
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "nvr_attn_prefill_paged_fp8: %s ops, D=%ld H=%ld KVH=%ld block_size=%ld (16-bit ops, D in {64,128}, H/KVH in {1,2,4}, "
+                         "block_size a power of two >= 64)", g_ops_f32 ? "float32" : "16-bit", (long)D, (long)H, (long)KVH, (long)bs);
     std::vector<int32_t> cu(m->batch + 1), ctxl(m->batch);
     NVR_HIP_CHECK(hipMemcpy(cu.data(), m->cu_seqlens_q, cu.size() * 4, hipMemcpyDeviceToHost));
     if (cu[m->batch] != T) return nvr::fail(NVR_ERR_LEN_MISMATCH, "cu_seqlens_q ends at %d but T=%ld", cu[m->batch], (long)T);
@@ -688,11 +693,19 @@ static int run_prefill_attn(const nvr_half *q, int64_t ldq, const nvr_half *kk, 
         k::FlashTile *d = nullptr;
         NVR_HIP_CHECK(hipMalloc((void **)&d, tiles.size() * sizeof(k::FlashTile) + 16));
         NVR_HIP_CHECK(hipMemcpy(d, tiles.data(), tiles.size() * sizeof(k::FlashTile), hipMemcpyHostToDevice));
-        k::FlashArgs f{};
-        f.q = q; f.ldq = ldq; f.k = kk; f.v = v; f.ldkv = ldkv; f.block_tables = m->block_tables; f.max_blocks = m->max_blocks;
-        f.block_size = (int32_t)bs; f.tiles = d; f.ntiles = (int32_t)tiles.size(); f.H = (int32_t)H; f.KVH = (int32_t)KVH; f.D = (int32_t)D;
-        f.scale = scale; f.out = out;
-        rc = KO(flash_prefill(f, paged, st));
+        if (kv_scales) {
+            k::FlashFp8Args f{};
+            f.q = q; f.ldq = ldq; f.k = (const uint8_t *)kk; f.v = (const uint8_t *)v; f.block_tables = m->block_tables; f.max_blocks = m->max_blocks;
+            f.block_size = (int32_t)bs; f.tiles = d; f.ntiles = (int32_t)tiles.size(); f.H = (int32_t)H; f.KVH = (int32_t)KVH; f.D = (int32_t)D;
+            f.scale = scale; f.k_scale = kv_scales[0]; f.v_scale = kv_scales[1]; f.out = out;
+            rc = KO(flash_prefill_fp8(f, st));
+        } else {
+            k::FlashArgs f{};
+            f.q = q; f.ldq = ldq; f.k = (const nvr_half *)kk; f.v = (const nvr_half *)v; f.ldkv = ldkv; f.block_tables = m->block_tables; f.max_blocks = m->max_blocks;
+            f.block_size = (int32_t)bs; f.tiles = d; f.ntiles = (int32_t)tiles.size(); f.H = (int32_t)H; f.KVH = (int32_t)KVH; f.D = (int32_t)D;
+            f.scale = scale; f.out = out;
+            rc = KO(flash_prefill(f, paged, st));
+        }
         hipStreamSynchronize(st);
         hipFree(d);
     } else {
@@ -709,7 +722,7 @@ static int run_prefill_attn(const nvr_half *q, int64_t ldq, const nvr_half *kk, 
         NVR_HIP_CHECK(hipMemcpy(d + T, ref.data(), T * 4, hipMemcpyHostToDevice));
         if (g_ops_f32) {
             nvr::kt::AttnArgsF f{};
-            f.q = FP(q); f.ldq = ldq; f.k = FP(kk); f.v = FP(v); f.ldkv = ldkv; f.ctx_lens = d; f.nq = (int32_t)T;
+            f.q = FP(q); f.ldq = ldq; f.k = (const float *)kk; f.v = (const float *)v; f.ldkv = ldkv; f.ctx_lens = d; f.nq = (int32_t)T;
             if (paged) { f.seq_of_q = d + T; f.block_tables = m->block_tables; f.max_blocks = m->max_blocks; f.block_size = (int32_t)bs; }
             else f.kv_base = d + T;
             f.H = (int32_t)H; f.KVH = (int32_t)KVH; f.D = (int32_t)D; f.scale = scale; f.max_ctx = maxc; f.out = FP(out);
@@ -719,7 +732,7 @@ static int run_prefill_attn(const nvr_half *q, int64_t ldq, const nvr_half *kk, 
             return rc;
         }
         k::AttnArgs a{};
-        a.q = q; a.ldq = ldq; a.k = kk; a.v = v; a.ldkv = ldkv; a.ctx_lens = d; a.nq = (int32_t)T;
+        a.q = q; a.ldq = ldq; a.k = (const nvr_half *)kk; a.v = (const nvr_half *)v; a.ldkv = ldkv; a.ctx_lens = d; a.nq = (int32_t)T;
         if (paged) { a.seq_of_q = d + T; a.block_tables = m->block_tables; a.max_blocks = m->max_blocks; a.block_size = (int32_t)bs; }
         else a.kv_base = d + T;
         a.H = (int32_t)H; a.KVH = (int32_t)KVH; a.D = (int32_t)D; a.scale = scale; a.max_ctx = maxc; a.out = out;
@@ -739,6 +752,13 @@ int nvr_attn_prefill_paged(const nvr_half *q, int64_t ldq, const nvr_half *kc, c
                            int64_t H, int64_t KVH, int64_t D, int64_t bs, float scale, nvr_half *out, void *s) {
     NVR_GUARD_BEGIN
     return run_prefill_attn(q, ldq, kc, vc, 0, m, true, bs, T, H, KVH, D, scale, out, (hipStream_t)s);
+    NVR_GUARD_END(NVR_ERR_INVARIANT)
+}
+int nvr_attn_prefill_paged_fp8(const nvr_half *q, int64_t ldq, const uint8_t *kc, const uint8_t *vc, const nvr_attn_meta *m, int64_t T, int64_t H, int64_t KVH,
+                               int64_t D, int64_t bs, float scale, float k_scale, float v_scale, nvr_half *out, void *s) {
+    NVR_GUARD_BEGIN
+    const float scales[2] = {k_scale, v_scale};
+    return run_prefill_attn(q, ldq, kc, vc, 0, m, true, bs, T, H, KVH, D, scale, out, (hipStream_t)s, scales);
     NVR_GUARD_END(NVR_ERR_INVARIANT)
 }
 int nvr_activation_type_from_str(const char *name, int32_t *type_out) {                       // ActivationType::from_str, activation.rs:169-182
