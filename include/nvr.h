@@ -108,8 +108,9 @@ typedef struct nvr_config {
                                           demand, bit-identical to the step's own).  Default 1 (r05; 0 in r02-r04). */
     int32_t shared_prefix_min_seqs;    /* decode batches of at least this many sequences that ALL begin with the same cache blocks
                                           (prefix-cache hits, block_manager.rs:181-197; BASELINE configs[4]) attend to those blocks in one
-                                          MFMA pass for the whole batch (nvr_paged_attn_decode_shared) instead of once per sequence; same
-                                          results within the attention tolerance.  0 = default (32), < 0 = never */
+                                          MFMA pass for the whole batch (nvr_paged_attn_decode_shared; kv_cache_dtype "fp8":
+                                          nvr_paged_attn_decode_shared_fp8, when kvcache_block_size is a power of two >= 64) instead of once per
+                                          sequence; same results within the attention tolerance.  0 = default (32), < 0 = never */
     char device[16];                   /* config.rs:48, validated like :108-111 plus "hip": "hip" (default) | "cuda" (the reference's
                                           default, taken as "the GPU") | "cpu" | "metal"; a runner exists only for "hip" / "cuda" —
                                           there is no CPU path in this library (NVR_ERR_UNSUPPORTED) */
@@ -134,8 +135,9 @@ typedef struct nvr_config {
                                           bytes (nvr_attn_prefill_paged_fp8) — so a prompt served behind a cached prefix or in chunks sees quantised K/V
                                           where the same prompt served whole sees its projections; decode always sees the bytes.  It needs a 16-bit dtype,
                                           head_dim 64 / 128 and 1, 2 or 4 query heads per kv head, and for recompute_cached_prefix = 0 or
-                                          enable_chunked_prefill = 1 a kvcache_block_size that is a power of two >= 64 (NVR_ERR_UNSUPPORTED otherwise); it
-                                          never takes the shared-prefix or the work-balanced decode launch.  Anything else: NVR_ERR_INVALID_ARG ("Unsupported kv_cache_dtype: ...") */
+                                          enable_chunked_prefill = 1 a kvcache_block_size that is a power of two >= 64 (NVR_ERR_UNSUPPORTED otherwise); with
+                                          such a block size it takes the shared-prefix decode launch (nvr_paged_attn_decode_shared_fp8), it never takes the
+                                          work-balanced one.  Anything else: NVR_ERR_INVALID_ARG ("Unsupported kv_cache_dtype: ...") */
 } nvr_config;
 NVR_API void nvr_config_default(nvr_config *cfg);                    /* config.rs:54-71 */
 NVR_API int nvr_config_validate(const nvr_config *cfg);              /* config.rs:83-119 */
@@ -608,6 +610,17 @@ NVR_API int nvr_paged_attn_decode_fp8(const nvr_half *q, int64_t ldq, const uint
                                       const nvr_attn_meta *meta, int64_t H, int64_t KVH, int64_t D, int64_t block_size,
                                       float scale, float k_scale, float v_scale, nvr_half *out, void *workspace,
                                       uint32_t *tickets /* nullable */, void *stream);
+/* nvr_paged_attn_decode_shared over such caches: the sequences of the batch (or rows[0 .. *count) of them) hold their first shared_len tokens (a
+ * multiple of block_size and of 64) in the same cache blocks; those keys go through one MFMA pass over the bytes for the whole group (bytes
+ * converted in registers, Q not quantised), the keys behind them per sequence through the kernel of nvr_paged_attn_decode_fp8, merged as
+ * split-KV partials.  Same semantics as nvr_paged_attn_decode_fp8.  rows / kv0 / count as for nvr_paged_attn_decode_shared (all three or all
+ * NULL, else NVR_ERR_INVALID_ARG, as are a shared_len that is no such multiple and a NULL workspace).  D in {64, 128}, H / KVH in {1, 2, 4},
+ * block_size a power of two >= 64; other shapes and "float32": NVR_ERR_UNSUPPORTED.  workspace: nvr_paged_attn_workspace_bytes. */
+NVR_API int nvr_paged_attn_decode_shared_fp8(const nvr_half *q, int64_t ldq, const uint8_t *k_cache, const uint8_t *v_cache,
+                                             const nvr_attn_meta *meta, int64_t H, int64_t KVH, int64_t D, int64_t block_size,
+                                             float scale, float k_scale, float v_scale, int64_t shared_len,
+                                             const int32_t *rows, const int32_t *kv0, const int32_t *count,
+                                             nvr_half *out, void *workspace, void *stream);
 /* K7 varlen causal prefill attention, attention.rs:177-208 (q,k,v inside packed qkv, stride ld) */
 NVR_API int nvr_attn_prefill_varlen(const nvr_half *q, const nvr_half *k, const nvr_half *v, int64_t ld,
                                     const nvr_attn_meta *meta, int64_t T, int64_t H, int64_t KVH, int64_t D,

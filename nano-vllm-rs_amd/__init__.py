@@ -239,6 +239,8 @@ _SIGS = {
     "nvr_kv_store_fp8": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float, _P, _P, _P]),
     "nvr_paged_attn_decode_fp8": (C.c_int, [_P, C.c_int64, _P, _P, C.POINTER(AttnMetaC), C.c_int64, C.c_int64, C.c_int64,
                                             C.c_int64, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "nvr_paged_attn_decode_shared_fp8": (C.c_int, [_P, C.c_int64, _P, _P, C.POINTER(AttnMetaC), C.c_int64, C.c_int64, C.c_int64,
+                                                   C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "nvr_attn_prefill_varlen": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(AttnMetaC), C.c_int64, C.c_int64, C.c_int64,
                                           C.c_int64, C.c_float, _P, _P]),
     "nvr_attn_prefill_paged": (C.c_int, [_P, C.c_int64, _P, _P, C.POINTER(AttnMetaC), C.c_int64, C.c_int64, C.c_int64, C.c_int64,

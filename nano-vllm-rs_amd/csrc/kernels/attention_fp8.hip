@@ -80,6 +80,9 @@ struct AttnFp8Params {
     float scale;                       // softmax scale x k_scale
     float v_scale;
     int32_t part_size, num_parts;
+    int32_t part0, kv0;                // shared-prefix decode: partitions 0..part0-1 hold the group's shared keys [0, kv0) (written by
+                                       // flash_shared_prefix_fp8); this launch covers partition part0 + i = keys [kv0 + i*part_size, ..)
+    const int32_t *kv0_rows;           // per-query kv0 (a group inside the batch: members shared_len, others 0) or null = kv0 for all
     float *part_o; float *part_ml;     // [nq, H, num_parts, D], [nq, H, num_parts, 2]
     half_t *out;                       // [nq, H, D]
 };
@@ -129,11 +132,12 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fp8_kernel(AttnFp8Params p) {
     constexpr int LPR = D / 16;         // lanes per byte row
     constexpr int RPI = 64 / LPR;       // rows per wave-instruction (= tokens per row group)
     constexpr int TPI = RPI * U;        // tokens per chunk
-    const int part = blockIdx.x % p.num_parts, g = (blockIdx.x / p.num_parts) % p.KVH;
-    const int t = blockIdx.x / (p.num_parts * p.KVH);
+    const int lparts = p.num_parts - p.part0;        // partitions of this launch
+    const int part = p.part0 + blockIdx.x % lparts, g = (blockIdx.x / lparts) % p.KVH;
+    const int t = blockIdx.x / (lparts * p.KVH);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int dc = lane % LPR, tg = lane / LPR;
-    const int p0 = part * p.part_size;
+    const int p0 = (p.kv0_rows ? p.kv0_rows[t] : p.kv0) + (part - p.part0) * p.part_size;   // (kv0: a multiple of 64, so UB chunks stay inside a block)
     const bool direct = p.num_parts == 1;
 
     const int32_t *bt = p.block_tables + (int64_t)t * p.max_blocks;
@@ -157,7 +161,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fp8_kernel(AttnFp8Params p) {
         }
     }
     const int ctx = p.ctx_lens[t];
-    if (p0 >= ctx && !direct) return;                // empty partition: the merge skips it too
+    if (p0 >= ctx && !direct) return;                // empty partition (or a member with no keys behind the prefix): the merge skips it too
     const int pend = max(p0, min(ctx, p0 + p.part_size));
     const int row_bytes = p.KVH * D;
 
@@ -336,14 +340,16 @@ __global__ __launch_bounds__(WAVES * 64) void attn_fp8_kernel(AttnFp8Params p) {
 // merge of the split-KV partials (merge_partitions: attn_merge.h; v_scale is already in them): D/4 threads per (query, head)
 template <int D>
 __global__ __launch_bounds__(256) void attn_fp8_merge_kernel(const float *__restrict__ part_o, const float *__restrict__ part_ml,
-                                                             const int32_t *__restrict__ ctx_lens, int H, int part_size, int num_parts, int64_t pairs,
-                                                             half_t *__restrict__ out) {
+                                                             const int32_t *__restrict__ ctx_lens, int H, int part_size, int num_parts, int part0,
+                                                             int kv0, const int32_t *__restrict__ kv0_rows, int64_t pairs, half_t *__restrict__ out) {
     constexpr int TPP = D / 4;
     const int64_t pair = (int64_t)blockIdx.x * (256 / TPP) + threadIdx.x / TPP;
     if (pair >= pairs) return;
     const int t = (int)(pair / H), d = (threadIdx.x % TPP) * 4;
-    const int np = min(num_parts, (ctx_lens[t] + part_size - 1) / part_size);
-    const int64_t base = pair * num_parts;
+    const int my_kv0 = kv0_rows ? kv0_rows[t] : kv0;
+    const int first = (part0 > 0 && my_kv0 == 0) ? part0 : 0;   // a query outside the sharing group has no partials in the shared slots
+    const int np = min(num_parts, part0 + (max(ctx_lens[t] - my_kv0, 0) + part_size - 1) / part_size) - first;
+    const int64_t base = pair * num_parts + first;
     const half4_t hv = merge_partitions(np,
         [&](int i) { return *reinterpret_cast<const float2_t *>(part_ml + (base + i) * 2); },
         [&](int i) { return *reinterpret_cast<const float4_t *>(part_o + (base + i) * D + d); });
@@ -370,13 +376,37 @@ static int launch_attn_fp8(const AttnFp8Args &a, hipStream_t s) {
     // given >= 64 keys each, the context cut into 64-key-granular partitions only to reach ~256 workgroups; fewer pairs: four waves and ~1024
     // workgroups; >= 2048 pairs of short contexts: two waves (a workgroup's life is mostly start-up and the cross-wave merge otherwise).
     const int64_t mc = a.max_ctx > 0 ? a.max_ctx : 1, pairs = (int64_t)a.nq * a.KVH, units = (mc + 63) / 64;
-    const int waves = !a.workspace ? 4 : (pairs >= 2048 && mc <= 512) ? 2 : pairs * units >= 256 ? 8 : 4;
-    int64_t want = 1;
-    if (a.workspace && waves == 8) want = pairs >= 192 ? 1 : (256 + pairs - 1) / pairs;
-    else if (a.workspace && waves == 4) want = (1024 + pairs - 1) / pairs;
-    want = std::max<int64_t>(1, std::min(want, units));
-    const int64_t ps = ((mc + want - 1) / want + 63) / 64 * 64;
-    const int np = (int)((mc + ps - 1) / ps);
+    int waves = !a.workspace ? 4 : (pairs >= 2048 && mc <= 512) ? 2 : pairs * units >= 256 ? 8 : 4;
+    int64_t ps; int np, sparts = 0, shared_part = 0;
+    if (a.shared_len > 0) {
+        // The plan of the 16-bit launch (attention.hip): the shared keys [0, shared_len) are cut into sparts equal partitions of 64-key granularity
+        // until the MFMA launch has ~256 workgroups; the keys behind them are partitioned like a context of their own (one partition per pair
+        // when there are enough pairs, else ~256 workgroups); always merged (np >= 2 keeps the partial format when nobody has own keys yet).
+        const int qb = 128 / G;                                           // flash_tile_positions
+        const int64_t wgs = (int64_t)((a.nq + qb - 1) / qb) * a.KVH, n64 = a.shared_len / 64;
+        int64_t c = std::min<int64_t>(std::max<int64_t>(1, (256 + wgs - 1) / wgs), n64);
+        while (n64 % c) --c;
+        sparts = (int)c;
+        const int64_t rest = std::max<int64_t>(a.shared_rows ? mc : mc - a.shared_len, 64);   // a query outside the group reads its whole context
+        // the workspace holds cap partials per (query, head): the shared partitions and the remainder's together must fit
+        const int64_t cap = a.workspace_bytes ? (int64_t)(a.workspace_bytes / ((size_t)a.nq * a.H * (D + 2) * sizeof(float))) : units;
+        if (cap < 2) return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: workspace too small for the shared-prefix pass");
+        while (sparts > 1 && sparts > cap / 2) { --sparts; while (n64 % sparts) --sparts; }
+        shared_part = a.shared_len / sparts;
+        int64_t want = pairs >= 192 ? 1 : (256 + pairs - 1) / pairs;
+        want = std::max<int64_t>(1, std::min<int64_t>(want, cap - sparts));
+        ps = ((rest + want - 1) / want + 63) / 64 * 64;
+        np = sparts + (int)((rest + ps - 1) / ps);
+        // own-key workgroups: two waves when there are >= 2048 of them over short partitions (the rule of the plain launch above), else four
+        waves = (pairs * (np - sparts) >= 2048 && ps <= 512) ? 2 : 4;
+    } else {
+        int64_t want = 1;
+        if (a.workspace && waves == 8) want = pairs >= 192 ? 1 : (256 + pairs - 1) / pairs;
+        else if (a.workspace && waves == 4) want = (1024 + pairs - 1) / pairs;
+        want = std::max<int64_t>(1, std::min(want, units));
+        ps = ((mc + want - 1) / want + 63) / 64 * 64;
+        np = (int)((mc + ps - 1) / ps);
+    }
     if (np > 1) {
         const size_t need = (size_t)a.nq * a.H * np * (D + 2) * sizeof(float);
         if (a.workspace_bytes && need > a.workspace_bytes)
@@ -385,14 +415,18 @@ static int launch_attn_fp8(const AttnFp8Args &a, hipStream_t s) {
         p.part_size = (int)ps; p.num_parts = np;
         p.part_o = (float *)a.workspace; p.part_ml = p.part_o + (int64_t)a.nq * a.H * np * D;
     } else { p.part_size = 0x3fffffff; p.num_parts = 1; }
-    const int64_t nwg = (int64_t)p.num_parts * a.KVH * a.nq;
+    p.part0 = sparts; p.kv0 = a.shared_len > 0 ? a.shared_len : 0; p.kv0_rows = a.shared_len > 0 ? a.shared_kv0 : nullptr;
+    if (sparts > 0)                                                      // partitions [0, sparts): the whole group's rows on the matrix cores
+        if (int rc = flash_shared_prefix_fp8(a.q, a.ldq, a.k, a.v, a.block_tables, a.max_blocks, a.block_size, a.nq, a.H, a.KVH, D, a.scale, a.k_scale, a.v_scale,
+                                             shared_part, sparts, np, p.part_o, p.part_ml, s, a.shared_rows, a.shared_count)) return rc;
+    const int64_t nwg = (int64_t)(p.num_parts - p.part0) * a.KVH * a.nq;
     if (waves == 8) launch_fp8_cfg<D, G, 8>(p, nwg, s);
     else if (waves == 4) launch_fp8_cfg<D, G, 4>(p, nwg, s);
     else launch_fp8_cfg<D, G, 2>(p, nwg, s);
     if (np > 1) {
         const int64_t rows = (int64_t)a.H * a.nq;
         attn_fp8_merge_kernel<D><<<dim3((unsigned)((rows + 256 / (D / 4) - 1) / (256 / (D / 4)))), dim3(256), 0, s>>>(p.part_o, p.part_ml, a.ctx_lens, a.H, p.part_size,
-                                                                                                                   np, rows, p.out);
+                                                                                                                   np, p.part0, p.kv0, p.kv0_rows, rows, p.out);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "attention_fp8 launch failed: %s", hipGetErrorString(e));
@@ -402,11 +436,20 @@ static int launch_attn_fp8(const AttnFp8Args &a, hipStream_t s) {
 int attention_fp8(const AttnFp8Args &a, hipStream_t s) {
     if (a.nq == 0) return 0;
     if (a.KVH <= 0 || a.H % a.KVH) return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: H=%d not a multiple of KVH=%d", a.H, a.KVH);
-    if (a.shared_len > 0 || a.balance_hint > 0)
-        return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: the shared-prefix pass and the work-balanced form exist for 16-bit caches only");
+    if (a.balance_hint > 0) return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: the work-balanced form exists for 16-bit caches only");
     if (!(a.k_scale > 0.f) || !(a.v_scale > 0.f)) return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: scales %g / %g (positive)", a.k_scale, a.v_scale);
     const int G = a.H / a.KVH;
     const bool shape_ok = (a.D == 64 || a.D == 128) && (G == 1 || G == 2 || G == 4);
+    if (a.shared_len > 0) {                                             // the shared-prefix pass (flash_shared_prefix_fp8 in front of the own-key partitions)
+        if (a.block_size <= 0 || a.shared_len % a.block_size || a.shared_len % 64 || !a.workspace)
+            return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: shared_len needs a workspace and whole blocks of whole 64-key steps (shared_len %d, block_size %d)",
+                             a.shared_len, a.block_size);
+        if ((a.shared_rows != nullptr) != (a.shared_kv0 != nullptr) || (a.shared_rows != nullptr) != (a.shared_count != nullptr))
+            return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: shared_rows / shared_kv0 / shared_count come together");
+        if (!flash_prefill_fp8_ok(a.D, a.H, a.KVH, a.block_size))
+            return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: the shared-prefix pass takes D in {64,128}, H/KVH in {1,2,4}, block_size a power of two >= 64 "
+                             "(D=%d H=%d KVH=%d block_size=%d)", a.D, a.H, a.KVH, a.block_size);
+    }
     if (!shape_ok || a.block_size < 64 / (a.D / 16))                    // a block holds at least one row group (8 rows at D = 128, 16 at D = 64)
         return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: unsupported head_dim=%d / group=%d / block_size=%d (D in {64,128}, G in {1,2,4}, block_size >= %d)",
                          a.D, G, a.block_size, shape_ok ? 64 / (a.D / 16) : 8);

@@ -38,6 +38,8 @@
 // Bytes behind a context: the last step of a tile clamps its key rows to the tile's last visible key (as the 16-bit kernel does), so rows at
 // or beyond the context — garbage, e4m3 NaN codes included — are never READ, let alone multiplied by a zero probability; block-table entries
 // past the context are never dereferenced.
+//
+// flash_shared_fp8_kernel (below): the same data path for the decode step's shared-prefix pass — decode rows in place of positions, no causal part.
 #include <type_traits>
 #include "kernels.h"
 #include "device_utils.h"
@@ -332,6 +334,241 @@ int flash_prefill_fp8(const FlashFp8Args &a, hipStream_t s) {
 #undef NVR_FLASH8
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "flash_prefill_fp8 launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// ---- shared-prefix decode pass -------------------------------------------------------------------------------------------------------
+// The decode step's attention over a prefix that every member of a group of sequences holds in the SAME cache blocks, byte-cache
+// counterpart of flash_prefill_kernel<.., SHARED = true> (flash_prefill.hip).  A kernel of its own, so flash_prefill_fp8_kernel keeps its
+// instructions; the data path is that kernel's (header comment), the differences are:
+//   * grid (ceil(nq / (128/G)) * KVH, sparts): a workgroup = one tile of 128/G DECODE ROWS (row i of the tile = srows[i] when a group is
+//     given, else i; rows at or beyond *scount / nq_total are clamped for the loads and never stored) x the G heads of one kv head x
+//     partition blockIdx.y = keys [y * part_len, (y + 1) * part_len) through the block-table row of the first member;
+//   * part_len is a multiple of the 64-key step and every key of it is visible to every row: no causal compare, no clamped last step, no
+//     wave that sits a step out — the loop is stage / K product / softmax / V product and nothing else;
+//   * the result leaves as a split-KV partial in the units of attn_fp8_kernel: f32 sums x v_scale, the maximum in SCALED units (raw
+//     maximum x softmax scale x k_scale), the sum of the 16-bit-rounded probabilities.
+// 2-slot ring and two workgroups per CU as in the prefill kernel: a launch is ~256 workgroups of part_len / 64 (2 at BASELINE configs[4])
+// steps, so step 1 is requested while step 0 is computed and nothing deeper could be in flight; other depths: not measured.
+struct FlashFp8SharedParams {
+    const half_t *q; int64_t ldq;
+    const uint8_t *k, *v;
+    const int32_t *block_tables; int32_t max_blocks, block_size, bs_shift;
+    int32_t H, KVH;
+    float scale;                       // softmax scale x k_scale
+    float v_scale;
+    int32_t nq_total, part_len, num_parts;
+    float *part_o, *part_ml;           // [nq, H, num_parts, D], [nq, H, num_parts, 2]
+    const int32_t *srows, *scount;     // optional group: member rows srows[0 .. *scount)
+};
+
+template <int D, int G>
+__global__ __launch_bounds__(256, 2) void flash_shared_fp8_kernel(FlashFp8SharedParams p) {
+    constexpr int NT = 256, KT = 64, QB = 128 / G;
+    constexpr int CPR = D / 16;
+    constexpr int PIECES = KT * CPR / NT;
+    constexpr int NKS = D / 32, NDT = D / 16, NQT = 2, NMT = KT / 16, NK2 = KT / 32;
+    constexpr int OPB = KT * D;
+    constexpr int STAGE = 2 * OPB;
+    static_assert(OPB == PIECES * NT * 16, "glds_pieces walks the pieces of the K image, then of the V image, NT * 16 bytes apart");
+    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+
+    const int g = blockIdx.x % p.KVH;
+    const int row0 = (int)(blockIdx.x / p.KVH) * QB;
+    const int nq = min(QB, (p.scount ? *p.scount : p.nq_total) - row0);
+    if (nq <= 0) return;                                              // (workgroup-uniform: the launch is sized for the whole batch)
+    const int kv_ref = p.srows ? p.srows[0] : 0;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = lane & 15, g4 = lane >> 4;
+    const int kv_start = (int)blockIdx.y * p.part_len;
+    const int nsteps = p.part_len / KT;
+
+    int head[NQT], qrow[NQT]; bool qvalid[NQT];
+    half8_t qf[NQT][NKS];
+#pragma unroll
+    for (int t = 0; t < NQT; ++t) {
+        int pblk;
+        if (G == 1) { head[t] = g; pblk = wave * 2 + t; }
+        else if (G == 2) { head[t] = g * 2 + t; pblk = wave; }
+        else { head[t] = g * 4 + (wave & 1) * 2 + t; pblk = wave >> 1; }
+        const int qi = pblk * 16 + r;
+        qvalid[t] = qi < nq;
+        const int qc = row0 + (qvalid[t] ? qi : nq - 1);
+        qrow[t] = p.srows ? p.srows[qc] : qc;
+        const half_t *qptr = p.q + (int64_t)qrow[t] * p.ldq + (int64_t)head[t] * D + g4 * 8;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) qf[t][ks] = *reinterpret_cast<const half8_t *>(qptr + ks * 32);
+    }
+
+    // register copy of 64 block-table entries, reloaded by the self-waiting asm load when the prefix spans more than 64 blocks
+    int bt_reg = 0, bt_chunk = -1;
+    auto load_bt_chunk = [&](int c) {
+        bt_chunk = c;
+        const int idx = min((c << 6) + lane, p.max_blocks - 1);
+        const int32_t *src = p.block_tables + (int64_t)kv_ref * p.max_blocks + idx;
+        asm volatile("global_load_dword %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=v"(bt_reg) : "v"(src) : "memory");
+    };
+    load_bt_chunk((kv_start >> p.bs_shift) >> 6);
+
+    const unsigned lds_ring = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    int64_t kconst[PIECES], vconst[PIECES];
+#pragma unroll
+    for (int i = 0; i < PIECES; ++i) {
+        const int idx = i * NT + threadIdx.x, row = idx / CPR, c = idx % CPR;
+        const int ksw = D == 128 ? (((row >> 1) & 1) | (((row >> 3) & 3) << 1)) : ((row >> 3) & 3);
+        const int vsw = D == 128 ? ((row >> 1) & 7) : ((row >> 2) & 3);
+        const int64_t rowoff = ((int64_t)row * p.KVH + g) * D;
+        kconst[i] = rowoff + (c ^ ksw) * 16;
+        vconst[i] = rowoff + (c ^ vsw) * 16;
+    }
+#pragma unroll
+    for (int t = 0; t < NQT; ++t)
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) asm volatile("" :: "v"(qf[t][ks]));
+    // a step = 64 consecutive rows of ONE cache block (block_size a power of two >= 64, kt a multiple of 64)
+    auto stage = [&](int buf, int kt) {
+        const uint8_t *src[2 * PIECES];
+        const int bi = kt >> p.bs_shift;
+        if ((bi >> 6) != bt_chunk) load_bt_chunk(bi >> 6);
+        const int64_t blk_row0 = (int64_t)__builtin_amdgcn_readlane(bt_reg, bi & 63) * p.block_size;
+        const int64_t sbase = (blk_row0 + (kt & (p.block_size - 1))) * p.KVH * D;
+#pragma unroll
+        for (int i = 0; i < PIECES; ++i) { src[i] = p.k + sbase + kconst[i]; src[PIECES + i] = p.v + sbase + vconst[i]; }
+        glds_pieces<2 * PIECES, NT * 16>(src, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_ring + buf * STAGE + wave_u * 1024)));
+    };
+
+    float4_t o[NQT][NDT], ol[NQT];
+    float m[NQT];
+#pragma unroll
+    for (int t = 0; t < NQT; ++t) {
+        m[t] = -INFINITY; ol[t] = (float4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NDT; ++i) o[t][i] = (float4_t){0.f, 0.f, 0.f, 0.f};
+    }
+    const float c2 = p.scale * 1.44269504088896340736f;
+    half8_t ones;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ones[e] = (half_t)1.0f;
+
+    const int krow = (r >> 2) * 8 + (r & 3);
+    const int kxor = k8_swz<D>(krow);
+    const int koff = krow * D + ((g4 & 1) << 3);
+    const int vrow = g4 * 8 + (r >> 1);
+    const int vxor = v8_swz<D>(vrow);
+    const int voff = vrow * D + ((r & 1) << 3);
+
+    auto step = [&](auto cur_c, int it) {
+        constexpr int cur = decltype(cur_c)::value;
+        if (it + 1 < nsteps) stage(cur ^ 1, kv_start + (it + 1) * KT);
+        const char *kl = smem + cur * STAGE, *vl = kl + OPB;
+
+        float4_t s[NQT][NMT];
+        int2_t kb[2][NKS];
+        auto read_k = [&](int mt, int2_t (&dst)[NKS]) {
+            const char *row = kl + ((mt >> 1) * 32 + (mt & 1) * 4) * D + koff;
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) dst[ks] = *reinterpret_cast<const int2_t *>(row + (((ks * 2 + (g4 >> 1)) ^ kxor) << 4));
+        };
+        read_k(0, kb[0]);
+#pragma unroll
+        for (int mt = 0; mt < NMT; ++mt) {
+            if (mt + 1 < NMT) read_k(mt + 1, kb[(mt + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < NQT; ++t) s[t][mt] = (float4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) {
+                const half8_t kf = fp8x8_to_half8(kb[mt & 1][ks]);
+#pragma unroll
+                for (int t = 0; t < NQT; ++t) s[t][mt] = mfma16(kf, qf[t][ks], s[t][mt]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        half8_t pf[NQT][NK2];
+        bool moved = false;
+        float alpha[NQT];
+#pragma unroll
+        for (int t = 0; t < NQT; ++t) {
+            float mx = fmaxf(fmaxf(s[t][0][0], s[t][0][1]), fmaxf(s[t][0][2], s[t][0][3]));
+#pragma unroll
+            for (int mt = 1; mt < NMT; ++mt) mx = fmaxf(fmaxf(mx, s[t][mt][0]), fmaxf(fmaxf(s[t][mt][1], s[t][mt][2]), s[t][mt][3]));
+            mx = max_over_rows(mx);
+            const float mn = fmaxf(m[t], mx);                   // finite from the first step on: all 64 keys are visible
+            alpha[t] = __builtin_amdgcn_exp2f((m[t] - mn) * c2);
+            moved |= mn != m[t];
+            m[t] = mn;
+            const float mc = -mn * c2;
+#pragma unroll
+            for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    pf[t][mt >> 1][(mt & 1) * 4 + e] = (half_t)__builtin_amdgcn_exp2f(fmaf(s[t][mt][e], c2, mc));
+        }
+        if (__any(moved)) {
+#pragma unroll
+            for (int t = 0; t < NQT; ++t) {
+                ol[t] *= alpha[t];
+#pragma unroll
+                for (int dt = 0; dt < NDT; ++dt) o[t][dt] *= alpha[t];
+            }
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < NK2; ++k2) {
+#pragma unroll
+            for (int t = 0; t < NQT; ++t) ol[t] = mfma16(ones, pf[t][k2], ol[t]);
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                const half8_t vf = fp8x8_to_half8(lds_read_tr8(vl + k2 * 32 * D + voff + ((dt ^ vxor) << 4)));
+#pragma unroll
+                for (int t = 0; t < NQT; ++t) o[t][dt] = mfma16(vf, pf[t][k2], o[t][dt]);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    };
+
+    stage(0, kv_start);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    for (int it = 0; it < nsteps; it += 2) {
+        step(std::integral_constant<int, 0>{}, it);
+        if (it + 1 < nsteps) step(std::integral_constant<int, 1>{}, it + 1);
+    }
+
+    // the partial of partition blockIdx.y: accumulator e of d-tile dt in lane group g4 is column 16·dt + 4·g4 + e of query r
+#pragma unroll
+    for (int t = 0; t < NQT; ++t) {
+        if (!qvalid[t]) continue;
+        const int64_t slot = ((int64_t)qrow[t] * p.H + head[t]) * p.num_parts + blockIdx.y;
+        float *po = p.part_o + slot * D + g4 * 4;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) *reinterpret_cast<float4_t *>(po + dt * 16) = o[t][dt] * p.v_scale;
+        if (g4 == 0) { p.part_ml[slot * 2] = m[t] * p.scale; p.part_ml[slot * 2 + 1] = ol[t][0]; }
+    }
+}
+
+// Partitions 0 .. sparts-1 (part_len keys each) of a decode step whose sequences (all nq, or the rows[0 .. *count) of them) share their first
+// sparts * part_len cached keys: f32 partials into slots (row, head, partition) of part_o [nq, H, num_parts, D] / part_ml [nq, H, num_parts, 2]
+int flash_shared_prefix_fp8(const half_bits *q, int64_t ldq, const uint8_t *k_cache, const uint8_t *v_cache, const int32_t *block_tables,
+                            int32_t max_blocks, int32_t block_size, int32_t nq, int32_t H, int32_t KVH, int32_t D, float scale, float k_scale,
+                            float v_scale, int32_t part_len, int32_t sparts, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s,
+                            const int32_t *rows, const int32_t *count) {
+    if (nq == 0) return 0;
+    if (!flash_prefill_fp8_ok(D, H, KVH, block_size) || part_len <= 0 || part_len % 64 || sparts < 1 || sparts > num_parts)
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "flash_shared_prefix_fp8: D=%d H=%d KVH=%d block_size=%d part_len=%d x %d", D, H, KVH, block_size, part_len, sparts);
+    FlashFp8SharedParams p{};
+    p.q = (const half_t *)q; p.ldq = ldq; p.k = k_cache; p.v = v_cache;
+    p.block_tables = block_tables; p.max_blocks = max_blocks; p.block_size = block_size; p.bs_shift = __builtin_ctz(block_size);
+    p.H = H; p.KVH = KVH; p.scale = scale * k_scale; p.v_scale = v_scale; p.nq_total = nq; p.part_len = part_len; p.num_parts = num_parts;
+    p.part_o = part_o; p.part_ml = part_ml; p.srows = rows; p.scount = count;
+    const int G = H / KVH, qb = 128 / G;
+    dim3 grid((unsigned)((int64_t)((nq + qb - 1) / qb) * KVH), (unsigned)sparts), block(256);
+#define NVR_FLASH8_S(DD, GG) if (D == DD && G == GG) flash_shared_fp8_kernel<DD, GG><<<grid, block, 0, s>>>(p);
+    NVR_FLASH8_S(128, 1) NVR_FLASH8_S(128, 2) NVR_FLASH8_S(128, 4) NVR_FLASH8_S(64, 1) NVR_FLASH8_S(64, 2) NVR_FLASH8_S(64, 4)
+#undef NVR_FLASH8_S
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "flash_shared_prefix_fp8 launch failed: %s", hipGetErrorString(e));
     return 0;
 }
 

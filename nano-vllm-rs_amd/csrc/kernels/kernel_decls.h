@@ -139,6 +139,11 @@ int flash_shared_prefix(const half_bits *q, int64_t ldq, const half_bits *k_cach
 // paged flash prefill over byte caches: D in {64,128}, H/KVH in {1,2,4}, block_size a power of two and a multiple of the 64-key step
 bool flash_prefill_fp8_ok(int D, int H, int KVH, int block_size);
 int flash_prefill_fp8(const FlashFp8Args &a, hipStream_t s);
+// flash_shared_prefix over byte caches: f32 partials (x v_scale, maximum in units of scale x k_scale) of partitions 0 .. sparts-1
+int flash_shared_prefix_fp8(const half_bits *q, int64_t ldq, const uint8_t *k_cache, const uint8_t *v_cache, const int32_t *block_tables,
+                            int32_t max_blocks, int32_t block_size, int32_t nq, int32_t H, int32_t KVH, int32_t D, float scale, float k_scale,
+                            float v_scale, int32_t part_len, int32_t sparts, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s,
+                            const int32_t *rows = nullptr, const int32_t *count = nullptr);
 
 // sampler (top-k / top-p / gumbel)
 size_t sample_workspace_bytes(int64_t B, int64_t V);

@@ -59,7 +59,9 @@ struct AttnFp8Args {
     int32_t max_ctx;                           // upper bound of ctx_lens (grid sizing)
     half_bits *out;                            // [nq, H, D] of the build's 16-bit type
     void *workspace; size_t workspace_bytes;   // split-KV partials (attn_workspace_bytes; bytes 0 = not checked)
-    int32_t shared_len, balance_hint;          // AttnArgs' shared-prefix pass / work-balanced form: not built for byte caches (> 0: NVR_ERR_UNSUPPORTED)
+    int32_t shared_len;                        // AttnArgs' shared-prefix pass (flash_shared_prefix_fp8; needs a workspace and a block_size that is a power of two >= 64)
+    int32_t balance_hint;                      // AttnArgs' work-balanced form: not built for byte caches (> 0: NVR_ERR_UNSUPPORTED)
+    const int32_t *shared_rows, *shared_kv0, *shared_count;   // as in AttnArgs: the group inside the batch (device arrays, all three or none)
 };
 
 // MFMA flash prefill attention.  A tile = up to 64/G consecutive query positions of one sequence.

@@ -899,6 +899,11 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
             f.ctx_lens = ctx; f.block_tables = bt; f.max_blocks = (int32_t)max_blocks_per_seq; f.block_size = (int32_t)block_size;
             f.nq = (int32_t)T; f.H = (int32_t)H; f.KVH = (int32_t)KVH; f.D = (int32_t)D; f.scale = scale; f.k_scale = k_scale; f.v_scale = v_scale;
             f.max_ctx = (int32_t)max_ctx; f.out = attn; f.workspace = attn_ws; f.workspace_bytes = attn_ws_bytes;
+            f.shared_len = (int32_t)decode_shared_len;
+            if (decode_shared_len > 0 && decode_shared_rows < T) {     // a group inside the batch: per-row kv0, member rows, member count
+                f.shared_kv0 = (const int32_t *)(in_dev + off_dec + dof_skv0); f.shared_rows = (const int32_t *)(in_dev + off_dec + dof_srows);
+                f.shared_count = (const int32_t *)(in_dev + off_dec + dof_scount);
+            }
             RC(KD(attention_fp8(f, st)));
         } else {                                                     // flash_attention_decode, attention.rs:225-235
             a.k = k_cache(l); a.v = v_cache(l); a.block_tables = bt; a.max_blocks = (int32_t)max_blocks_per_seq;
@@ -1119,7 +1124,10 @@ int nvr_model_runner::execute(nvr_seq *const *seqs, size_t nseq, bool is_prefill
         decode_shared_len = shared_prefix_plan(seqs, nseq, (int32_t *)(hd + dof_skv0), (int32_t *)(hd + dof_srows), (int32_t *)(hd + dof_scount),
                                                &decode_shared_rows);
         decode_ragged = ragged_batch(nseq, sum_ctx, (cfg.enforce_eager || graphs_disabled) ? max_ctx : (max_ctx + 255) / 256 * 256);
-        if (kv_fp8) { decode_shared_len = 0; decode_shared_rows = 0; decode_ragged = false; }   // attention_fp8 has neither form
+        if (kv_fp8) {                                        // attention_fp8 has no work-balanced form, and its shared pass takes whole 64-key steps of one block
+            decode_ragged = false;
+            if (!KD(flash_prefill_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size))) { decode_shared_len = 0; decode_shared_rows = 0; }
+        }
     }
     // one H2D per array actually used this step (K19)
     auto up = [&](size_t off, size_t bytes) { return hipMemcpyAsync(in_dev + off, in_host + off, bytes, hipMemcpyHostToDevice, stream); };
@@ -1214,7 +1222,10 @@ int nvr_model_runner::execute_decode_ahead(nvr_seq *const *seqs, size_t nseq, in
     decode_shared_len = shared_prefix_plan(seqs, nseq, (int32_t *)(hd + dof_skv0), (int32_t *)(hd + dof_srows), (int32_t *)(hd + dof_scount),
                                            &decode_shared_rows);
     decode_ragged = ragged_batch(nseq, sum_ctx, (cfg.enforce_eager || graphs_disabled) ? max_ctx : (max_ctx + 255) / 256 * 256);
-    if (kv_fp8) { decode_shared_len = 0; decode_shared_rows = 0; decode_ragged = false; }
+    if (kv_fp8) {
+        decode_ragged = false;
+        if (!KD(flash_prefill_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size))) { decode_shared_len = 0; decode_shared_rows = 0; }
+    }
     NVR_HIP_CHECK(hipMemcpyAsync(in_dev + off_dec + dof_pos, hd + dof_pos, dof_bt + nseq * max_blocks_per_seq * 4 - dof_pos, hipMemcpyHostToDevice, stream));
     last_rows = nseq; last_prefill = false; last_tokens = (int64_t)nseq;
     lm_parts = KD(lm_head_parts((int64_t)nseq, Hd, Vl, Hd));

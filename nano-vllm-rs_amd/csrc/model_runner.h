@@ -52,7 +52,8 @@ struct nvr_model_runner {
     size_t kv_elem_bytes = 2;              // bytes of a cache element: 2 (fp16 / bf16), 4 (float32) or 1 (kv_fp8)
     // nvr_config.kv_cache_dtype = "fp8": the pool holds OCP e4m3 bytes, value = byte * scale (kernels/attention_fp8.hip).  The projection launches of a
     // step get no_slots (all -1: they store no cache row) and one kv_store_fp8 launch per layer quantises the roped K / V columns of qkv; prefill attention
-    // of whole prompts reads qkv, behind a cached prefix or in a later chunk it is flash_prefill_fp8 over the bytes; decode attention is attention_fp8.
+    // of whole prompts reads qkv, behind a cached prefix or in a later chunk it is flash_prefill_fp8 over the bytes; decode attention is attention_fp8
+    // (with its shared-prefix pass when flash_prefill_fp8_ok holds).
     bool kv_fp8 = false, stepped = false;  // stepped: a step has been executed (the scales are fixed from then on)
     float k_scale = 1.f, v_scale = 1.f;
     int32_t *no_slots = nullptr;           // [max(max_tokens, max_seqs)] of -1

@@ -668,6 +668,17 @@ int nvr_paged_attn_decode_fp8(const nvr_half *q, int64_t ldq, const uint8_t *kc,
     a.v_scale = v_scale; a.max_ctx = m->max_context_len; a.out = out; a.workspace = ws;
     return KO(attention_fp8(a, (hipStream_t)s));
 }
+int nvr_paged_attn_decode_shared_fp8(const nvr_half *q, int64_t ldq, const uint8_t *kc, const uint8_t *vc, const nvr_attn_meta *m, int64_t H, int64_t KVH,
+                                     int64_t D, int64_t bs, float scale, float k_scale, float v_scale, int64_t shared_len, const int32_t *rows,
+                                     const int32_t *kv0, const int32_t *count, nvr_half *out, void *ws, void *s) {
+    if (g_ops_f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "nvr_paged_attn_decode_shared_fp8: 16-bit queries and outputs (nvr_ops_set_dtype float16 | bfloat16)");
+    k::AttnFp8Args a{};
+    a.q = q; a.ldq = ldq; a.k = kc; a.v = vc; a.ctx_lens = m->context_lens; a.block_tables = m->block_tables; a.max_blocks = m->max_blocks;
+    a.block_size = (int32_t)bs; a.nq = m->batch; a.H = (int32_t)H; a.KVH = (int32_t)KVH; a.D = (int32_t)D; a.scale = scale; a.k_scale = k_scale;
+    a.v_scale = v_scale; a.max_ctx = m->max_context_len; a.out = out; a.workspace = ws;
+    a.shared_len = (int32_t)shared_len; a.shared_rows = rows; a.shared_kv0 = kv0; a.shared_count = count;
+    return KO(attention_fp8(a, (hipStream_t)s));
+}
 // host-side tile list for the flash kernels from cu_seqlens_q (+ context lens for the paged variant)
 // (kv_scales: null, or {k_scale, v_scale} of byte caches behind kk / v — the paged fp8 kernel, which has no row-kernel counterpart)
 static int run_prefill_attn(const nvr_half *q, int64_t ldq, const void *kk, const void *v, int64_t ldkv, const nvr_attn_meta *m,
