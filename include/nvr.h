@@ -138,6 +138,16 @@ typedef struct nvr_config {
                                           enable_chunked_prefill = 1 a kvcache_block_size that is a power of two >= 64 (NVR_ERR_UNSUPPORTED otherwise); with
                                           such a block size it takes the shared-prefix decode launch (nvr_paged_attn_decode_shared_fp8), it never takes the
                                           work-balanced one.  Anything else: NVR_ERR_INVALID_ARG ("Unsupported kv_cache_dtype: ...") */
+    char decode_weight_dtype[16];      /* extension (the reference streams 16-bit weights): "" | "auto" (default): nothing changes, bit for bit; "fp8" |
+                                          "fp8_e4m3": steps of <= 64 rows stream the four projection weights of every layer as OCP e4m3 bytes with one
+                                          power-of-two f32 scale per output row (nvr_weight_quantize_fp8 / nvr_linear_fp8, nvr_linear_silu_mul_fp8,
+                                          nvr_linear_splitk_fp8) — the byte copy REPLACES the tiled 16-bit copy (3 instead of 4 weight bytes per element), and the
+                                          row-major weights are overwritten by their dequantised values at creation and after nvr_runner_load_tensor, so larger
+                                          steps (prefill) compute with the same weight values through the 16-bit GEMMs and nvr_runner_copy_weight returns the
+                                          dequantised values.  Activations are not quantised; embedding and LM head stay 16-bit.  Independent of
+                                          kv_cache_dtype.  It needs a 16-bit dtype, no biases, tensor_parallel_size 1 and hidden, heads x head_dim and
+                                          intermediate sizes that are multiples of 64 (NVR_ERR_UNSUPPORTED otherwise).  Anything else: NVR_ERR_INVALID_ARG
+                                          ("Unsupported decode_weight_dtype: ...") */
 } nvr_config;
 NVR_API void nvr_config_default(nvr_config *cfg);                    /* config.rs:54-71 */
 NVR_API int nvr_config_validate(const nvr_config *cfg);              /* config.rs:83-119 */
@@ -275,6 +285,9 @@ NVR_API uint64_t nvr_runner_num_kvcache_blocks(const nvr_model_runner_t *r);
 NVR_API int nvr_runner_kv_cache(nvr_model_runner_t *r, size_t layer, void **k_dev, void **v_dev);
 /* element type of that pool: "float16" | "bfloat16" | "float32" | "fp8_e4m3" (create_kv_cache's dtype argument, model_runner.rs:364-396) */
 NVR_API const char *nvr_runner_kv_cache_dtype(const nvr_model_runner_t *r);
+/* what steps of <= 64 rows stream as projection weights: "float16" | "bfloat16" | "float32" (the runner's dtype), or "fp8_e4m3"
+ * (nvr_config.decode_weight_dtype = "fp8": nvr_runner_copy_weight then returns the DEQUANTISED weights, the values every step computes with) */
+NVR_API const char *nvr_runner_decode_weight_dtype(const nvr_model_runner_t *r);
 /* scales of an fp8 KV cache (stored byte = e4m3(x / scale), both default 1.0; model_runner.rs:364-396 has no counterpart): before the
  * first step only — the cache rows already written hold the old scales (NVR_ERR_INVARIANT afterwards; NVR_ERR_INVALID_ARG unless both are
  * positive and finite; NVR_ERR_UNSUPPORTED on a runner whose cache is not fp8) */
@@ -537,6 +550,21 @@ NVR_API int nvr_linear_splitk_tiled(const nvr_half *x, int64_t ldx, const nvr_ha
                                     int64_t N, int64_t S, float *slabs, void *stream);
 NVR_API int nvr_linear_silu_mul_tiled(const nvr_half *x, int64_t ldx, const nvr_half *W, const nvr_half *Wt, int64_t T, int64_t K,
                                       int64_t I, nvr_half *out, void *stream);
+/* FP8 (OCP e4m3fn) weight stream of decode-sized GEMMs (kernels/linear_fp8.hip; 16-bit ops dtypes only).  nvr_weight_quantize_fp8: row-major
+ * W[N][K] (N % 16 == 0, K % 64 == 0; finite, |w| <= 2^15) -> Wq, N*K bytes tiled [N/16][K/64][64 lanes][16 B] (lane 16q + r: row 16 tile + r,
+ * columns 64 kb + 8q + 0..7 and 64 kb + 32 + 8q + 0..7), scales[N] = 2^e with e the smallest integer such that amax(row) <= 448 * 2^e, e >= -15
+ * (all-zero row: e = 0), byte = e4m3(w / 2^e) rounded to nearest even and clamped to +-448, and, if Wd is not NULL (it may be W), the dequantised
+ * weights byte * 2^e as row-major 16-bit values — exact in fp16 and bf16.  The GEMMs compute x[T][K] (row stride ldx, a multiple of 8) times
+ * (scales[n] * e4m3(Wq[n][k]))^T for T <= 64 with the epilogues and rounding points of nvr_linear (16-bit y[T][N]), nvr_linear_silu_mul (W is
+ * [2I][K], out [T][I]) and nvr_linear_splitk (f32 slabs [S][T][N] for nvr_add_rmsnorm_slabs; S divides K / 64); activations are not quantised.
+ * NVR_ERR_UNSUPPORTED for other shapes and for the float32 ops dtype, NVR_ERR_INVALID_ARG for null pointers. */
+NVR_API int nvr_weight_quantize_fp8(const nvr_half *W, int64_t N, int64_t K, uint8_t *Wq, float *scales, nvr_half *Wd_or_null, void *stream);
+NVR_API int nvr_linear_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, nvr_half *y,
+                           void *stream);
+NVR_API int nvr_linear_silu_mul_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t I,
+                                    nvr_half *out, void *stream);
+NVR_API int nvr_linear_splitk_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N,
+                                  int64_t S, float *slabs, void *stream);
 NVR_API int nvr_linear_qkv_rope_store_tiled(const nvr_half *x, int64_t ldx, const nvr_half *W, const nvr_half *Wt, int64_t T,
                                             int64_t K, int64_t H, int64_t KVH, int64_t D, const int64_t *positions,
                                             const int32_t *slot_mapping, const float *cos_t, const float *sin_t,

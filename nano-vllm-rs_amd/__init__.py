@@ -55,7 +55,8 @@ class ConfigC(C.Structure):
                 ("tensor_parallel_rank", C.c_uint64), ("device_ordinal", C.c_int32), ("sample_seed", C.c_uint64),
                 ("skip_block_size_check", C.c_int32), ("decode_chain", C.c_uint32),
                 ("recompute_cached_prefix", C.c_int32), ("enable_chunked_prefill", C.c_int32), ("async_decode", C.c_int32), ("shared_prefix_min_seqs", C.c_int32),
-                ("device", C.c_char * 16), ("dtype", C.c_char * 16), ("kv_cache_dtype", C.c_char * 16)]
+                ("device", C.c_char * 16), ("dtype", C.c_char * 16), ("kv_cache_dtype", C.c_char * 16),
+                ("decode_weight_dtype", C.c_char * 16)]
 
 
 class ModelConfigC(C.Structure):
@@ -163,6 +164,7 @@ _SIGS = {
     "nvr_runner_copy_logits": (C.c_int, [_P, _P, C.c_size_t]),
     "nvr_runner_num_kvcache_blocks": (C.c_uint64, [_P]),
     "nvr_runner_kv_cache": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), C.POINTER(_P)]),
+    "nvr_runner_decode_weight_dtype": (C.c_char_p, [_P]),
     "nvr_runner_kv_cache_dtype": (C.c_char_p, [_P]), "nvr_runner_set_kv_scales": (C.c_int, [_P, C.c_float, C.c_float]),
     "nvr_runner_stream": (_P, [_P]), "nvr_comm_unique_id": (C.c_int, [_P]),
     "nvr_runner_init_comm": (C.c_int, [_P, _P]), "nvr_runner_comm_selftest": (C.c_int, [_P]),
@@ -219,6 +221,10 @@ _SIGS = {
     "nvr_linear_qkv_rope_store_tiled": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P,
                                                   _P, _P, _P, _P]),
     "nvr_lm_head_tiled": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    "nvr_weight_quantize_fp8": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "nvr_linear_fp8": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    "nvr_linear_silu_mul_fp8": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    "nvr_linear_splitk_fp8": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "nvr_retile_weight": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P]),
     "nvr_decode_splitk_slices": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
     "nvr_linear_add_residual": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
@@ -677,6 +683,10 @@ class ModelRunner:
     def kv_cache_dtype(self) -> str:
         """Element type of the KV pool: "float16" | "bfloat16" | "float32", or "fp8_e4m3" (Config(kv_cache_dtype="fp8"): one byte per element)."""
         return lib().nvr_runner_kv_cache_dtype(self.h).decode()
+
+    def decode_weight_dtype(self) -> str:
+        """What steps of <= 64 rows stream as projection weights: the runner's dtype, or "fp8_e4m3" (Config(decode_weight_dtype="fp8"))."""
+        return lib().nvr_runner_decode_weight_dtype(self.h).decode()
 
     def set_kv_scales(self, k_scale: float, v_scale: float) -> None:
         """Scales of an fp8 KV cache (stored byte = e4m3(x / scale)); before the first step only."""

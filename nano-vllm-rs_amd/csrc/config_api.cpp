@@ -26,6 +26,7 @@ void nvr_config_default(nvr_config *c) {                             // config.r
     c->async_decode = 1;                                                  // launch-ahead of greedy decode steps: transparent (same batches, tokens, statistics)
     std::strcpy(c->device, "hip"); std::strcpy(c->dtype, "float16");     // config.rs:67-68 ("cuda" there)
     std::strcpy(c->kv_cache_dtype, "auto");                              // the cache has the runner's dtype
+    std::strcpy(c->decode_weight_dtype, "auto");                         // decode-sized steps stream the 16-bit weights
 }
 static bool cfg_str_in(const char *v, size_t cap, std::initializer_list<const char *> set) {
     if (!std::memchr(v, 0, cap)) return false;
@@ -54,6 +55,8 @@ int nvr_config_validate(const nvr_config *c) {                       // config.r
         return nvr::fail(NVR_ERR_INVALID_ARG, "Unsupported dtype: %.15s", c->dtype);
     if (!cfg_str_in(c->kv_cache_dtype, sizeof c->kv_cache_dtype, {"", "auto", "fp8", "fp8_e4m3"}))
         return nvr::fail(NVR_ERR_INVALID_ARG, "Unsupported kv_cache_dtype: %.15s", c->kv_cache_dtype);
+    if (!cfg_str_in(c->decode_weight_dtype, sizeof c->decode_weight_dtype, {"", "auto", "fp8", "fp8_e4m3"}))
+        return nvr::fail(NVR_ERR_INVALID_ARG, "Unsupported decode_weight_dtype: %.15s", c->decode_weight_dtype);
     if (c->decode_chain != 0 && c->decode_chain != 6)
         return nvr::fail(NVR_ERR_INVALID_ARG, "decode_chain must be 0 (reserved; 6 = the same six-launch chain), got %u", c->decode_chain);
     return NVR_OK;

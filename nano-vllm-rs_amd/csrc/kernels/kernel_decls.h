@@ -86,6 +86,18 @@ int linear_stream_qkv_rope_store(const half_bits *x, int64_t ldx, const half_bit
                                  const int64_t *positions, const int32_t *slots, const float *cos_t, const float *sin_t, half_bits *qkv,
                                  half_bits *k_cache, half_bits *v_cache, hipStream_t s, const half_bits *Wt = nullptr);
 
+// FP8 (e4m3) weight stream of decode-sized GEMMs (linear_fp8.hip): T <= 64, K % 64 == 0, N % 16 == 0, ldx % 8 == 0.  weight_quantize_fp8: row-major
+// W[N, K] -> tiled bytes Wq [N/16][K/64][64][16], one power-of-two f32 scale per row and (Wd non-null, may be W) the dequantised weights, exactly.
+// The GEMMs compute x · (scales[n] · e4m3(Wq[n, k]))^T with the epilogues and rounding points of linear / linear_silu_mul / linear_splitk.
+int linear_fp8_prepare();                                                   // LDS opt-in of every instance (call outside captures)
+bool linear_fp8_ok(int64_t T, int64_t K, int64_t N, int64_t ldx);
+int weight_quantize_fp8(const half_bits *W, int64_t N, int64_t K, uint8_t *Wq, float *scales, half_bits *Wd, hipStream_t s);
+int linear_fp8(const half_bits *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, half_bits *y, hipStream_t s);
+int linear_silu_mul_fp8(const half_bits *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t I, half_bits *out,
+                        hipStream_t s);
+int linear_splitk_fp8(const half_bits *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, int64_t S, float *slabs,
+                      hipStream_t s);
+
 // LM head over more than 32 rows: the 128x128 kernel with the logits / arg-max epilogue (one partial per 128-column tile)
 bool gemm_tiled_splitk_ok(int64_t T, int64_t K, int64_t N, int64_t S, int64_t ldx);
 int gemm_tiled_splitk(const half_bits *x, int64_t ldx, const half_bits *W, int64_t T, int64_t K, int64_t N, int64_t S, float *slabs, hipStream_t s);

@@ -42,7 +42,7 @@ nvr_model_runner::~nvr_model_runner() {
     comm.destroy();
     if (attn_tickets) hipFree(attn_tickets);
     for (auto &l : layers) { hipFree(l.qkv); hipFree(l.o); hipFree(l.gate_up); hipFree(l.down); hipFree(l.ln1); hipFree(l.ln2);
-                             void *ts[] = {l.qkv_t, l.o_t, l.gate_up_t, l.down_t, l.q_norm, l.k_norm, l.qkv_b, l.o_b, l.gate_up_b, l.down_b}; for (void *t : ts) if (t) hipFree(t); }
+                             void *ts[] = {l.qkv_t, l.o_t, l.gate_up_t, l.down_t, l.qkv_s, l.o_s, l.gate_up_s, l.down_s, l.q_norm, l.k_norm, l.qkv_b, l.o_b, l.gate_up_b, l.down_b}; for (void *t : ts) if (t) hipFree(t); }
     if (lm_head_t) hipFree(lm_head_t);
     void *ptrs[] = {embed, mc.tie_word_embeddings ? nullptr : lm_head, norm, cos_t, sin_t, kv_pool, h, n, qkv, attn,
                     proj, gu, act, nlast, logits, attn_ws, slabs, in_dev, d_tok, d_maxval, d_temp, d_topk, d_topp, d_keys,
@@ -66,6 +66,12 @@ int nvr_model_runner::init() {                                       // ModelRun
     kv_fp8 = std::strncmp(cfg.kv_cache_dtype, "fp8", 3) == 0;                     // "fp8" | "fp8_e4m3" (nvr_config_validate has seen the name)
     kv_elem_bytes = kv_fp8 ? 1 : f32 ? 4 : 2;
     if (kv_fp8 && f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8 needs dtype float16 or bfloat16 (the fp8 kernels quantise and read 16-bit rows)");
+    w_fp8 = std::strncmp(cfg.decode_weight_dtype, "fp8", 3) == 0;                 // "fp8" | "fp8_e4m3"
+    if (w_fp8 && f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "decode_weight_dtype fp8 needs dtype float16 or bfloat16 (the byte stream feeds the 16-bit MFMAs)");
+    if (w_fp8 && cfg.tensor_parallel_size > 1)
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "decode_weight_dtype fp8 needs tensor_parallel_size 1 (got %lu): the row-parallel exchange paths read 16-bit projections",
+                         (unsigned long)cfg.tensor_parallel_size);
+    if (w_fp8 && mc.use_bias) return nvr::fail(NVR_ERR_UNSUPPORTED, "decode_weight_dtype fp8 does not take use_bias models (the byte-stream GEMMs have no bias epilogue)");
     if (f32) { tiled_weights = false; lm_fused = false; RC(nvr::kf::prepare()); }   // (decode steps of the f32 path replay a captured graph like the 16-bit ones)
     comm.bf16 = bf16;                                                              // the collectives round their sums to the same 16-bit type
     if (tp < 1 || rank >= tp) return nvr::fail(NVR_ERR_INVALID_ARG, "bad tensor parallel rank %ld of %ld", (long)rank, (long)tp);
@@ -110,6 +116,9 @@ int nvr_model_runner::init() {                                       // ModelRun
         }
     }
 
+    if (w_fp8 && (!env.tiled_weights || Hd % 64 || (H * D) % 64 || I % 64 || D % 16))
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "decode_weight_dtype fp8 needs the decode weight copies (NVR_TILED_WEIGHTS) and hidden %ld, heads x head_dim %ld, intermediate "
+                         "%ld that are multiples of 64", (long)Hd, (long)(H * D), (long)I);
     RC(gen_weights());
 
     // RoPE tables (rotary_embedding.rs:74-119, A-14): computed on the host in f64 from the f32 angle,
@@ -147,6 +156,7 @@ int nvr_model_runner::init() {                                       // ModelRun
     if (!env.tp_graph && tp > 1) graphs_disabled = true;
     comm.force = env.tp_force_comm; comm.timeout_ms = env.p2p_timeout_ms; comm.p2p_fenced = env.p2p_fenced;
     RC(KD(linear_stream_prepare()));
+    if (w_fp8) RC(KD(linear_fp8_prepare()));
     RC(KD(gemm_tiled_prepare()));
     lazy_logits = env.lazy_logits && !f32;
     {   // arg-max partials [parts][rows]: <= LM_HEAD_MAX_PARTS x 32 rows (lm_head_kernel), or one per 128 vocabulary columns x all rows
@@ -236,6 +246,13 @@ int nvr_model_runner::retile_all() {
     const bool gemm_ok = Hd % 32 == 0 && (H * D) % 32 == 0 && I % 32 == 0 && QKV % 16 == 0 && Hd % 16 == 0 && I % 16 == 0 && D % 16 == 0;
     for (auto &w : layers) {
         if (!gemm_ok || !w.qkv_t) continue;
+        if (w_fp8) {                             // bytes + row scales; the row-major weight becomes its dequantised self (idempotent: a fixed point)
+            RC(KD(weight_quantize_fp8(w.qkv, QKV, Hd, reinterpret_cast<uint8_t *>(w.qkv_t), w.qkv_s, w.qkv, stream)));
+            RC(KD(weight_quantize_fp8(w.o, Hd, H * D, reinterpret_cast<uint8_t *>(w.o_t), w.o_s, w.o, stream)));
+            RC(KD(weight_quantize_fp8(w.gate_up, 2 * I, Hd, reinterpret_cast<uint8_t *>(w.gate_up_t), w.gate_up_s, w.gate_up, stream)));
+            RC(KD(weight_quantize_fp8(w.down, Hd, I, reinterpret_cast<uint8_t *>(w.down_t), w.down_s, w.down, stream)));
+            continue;
+        }
         RC(KD(retile_weight(w.qkv, w.qkv_t, QKV, Hd, (mc.qk_norm || mc.use_bias) ? 0 : 1, H, KVH, D, stream)));   // qk_norm / use_bias: plain GEMM, rows in place
         RC(KD(retile_weight(w.o, w.o_t, Hd, H * D, 0, 0, 0, 0, stream)));
         RC(KD(retile_weight(w.gate_up, w.gate_up_t, 2 * I, Hd, 0, 0, 0, 0, stream)));
@@ -394,6 +411,7 @@ int nvr_model_runner::gen_weights() {
         RC(dmalloc(&w.qkv, QKV * Hd)); RC(dmalloc(&w.o, Hd * H * D)); RC(dmalloc(&w.gate_up, 2 * I * Hd));
         RC(dmalloc(&w.down, Hd * I)); RC(dmalloc(&w.ln1, Hd)); RC(dmalloc(&w.ln2, Hd));
         w.qkv_t = w.o_t = w.gate_up_t = w.down_t = w.q_norm = w.k_norm = nullptr;
+        w.qkv_s = w.o_s = w.gate_up_s = w.down_s = nullptr;
         w.qkv_b = w.o_b = w.gate_up_b = w.down_b = nullptr;
         if (mc.use_bias) {
             // Qwen3Config::use_bias: one value per output feature, generated like a one-column weight indexed by the GLOBAL output row (shards
@@ -414,7 +432,10 @@ int nvr_model_runner::gen_weights() {
             RC(dmalloc(&w.q_norm, D)); RC(dmalloc(&w.k_norm, D));
             RC(KD(fill_const(w.q_norm, D, 1.0f, stream))); RC(KD(fill_const(w.k_norm, D, 1.0f, stream)));
         }
-        if (tiled_weights) {
+        if (tiled_weights && w_fp8) {            // one byte per element (the sizes are multiples of 64) and a scale per output row
+            RC(dmalloc(&w.qkv_t, QKV * Hd / 2)); RC(dmalloc(&w.o_t, Hd * H * D / 2)); RC(dmalloc(&w.gate_up_t, 2 * I * Hd / 2)); RC(dmalloc(&w.down_t, Hd * I / 2));
+            RC(dmalloc(&w.qkv_s, QKV)); RC(dmalloc(&w.o_s, Hd)); RC(dmalloc(&w.gate_up_s, 2 * I)); RC(dmalloc(&w.down_s, Hd));
+        } else if (tiled_weights) {
             RC(dmalloc(&w.qkv_t, QKV * Hd)); RC(dmalloc(&w.o_t, Hd * H * D)); RC(dmalloc(&w.gate_up_t, 2 * I * Hd)); RC(dmalloc(&w.down_t, Hd * I));
         }
         // QKVParallelLinear, linear.rs:300-340: global rows [q heads | k heads | v heads], per-rank head slices
@@ -596,7 +617,19 @@ int nvr_model_runner::copy_weight(const char *ln, uint16_t *out, size_t cap, int
 // slabs are summed, added to the residual and normalised by the following add_rmsnorm_slabs launch.  Otherwise the plain kernel
 // writes fp16 `proj` (+ all-reduce when tensor parallel) and add_rmsnorm follows.
 int nvr_model_runner::row_parallel_norm(const uint16_t *x, int64_t K, const uint16_t *W, const uint16_t *Wt, int64_t T, const uint16_t *wn,
-                                        const uint16_t *bias) {
+                                        const uint16_t *bias, const float *w_scales) {
+    if (w_scales) {                              // w_fp8, <= 64 rows: the byte stream's split-k form (one rank, no bias: init)
+        // slices: decode_splitk_slices' count, but at least the 4 that give every workgroup of a slice its full set of tiles at hidden 4096 (256 tiles), cut
+        // down to a divisor of K / 64 (whole 64-column tiles per slice); add_rmsnorm_slabs sums 2, 4 or 8 slabs — K / 64 odd: the plain form + add_rmsnorm
+        int64_t S = std::max<int64_t>(4, KD(decode_splitk_slices(T, K, Hd)));
+        while (S > 1 && ((K / 64) % S || S * T > 4 * slab_rows)) S /= 2;
+        if (S < 2) {
+            RC(KD(linear_fp8(x, K, reinterpret_cast<const uint8_t *>(Wt), w_scales, T, K, Hd, proj, stream)));
+            return KD(add_rmsnorm(h, proj, wn, mc.rms_norm_eps, T, Hd, n, stream));
+        }
+        RC(KD(linear_splitk_fp8(x, K, reinterpret_cast<const uint8_t *>(Wt), w_scales, T, K, Hd, S, slabs, stream)));
+        return KD(add_rmsnorm_slabs(h, slabs, S, wn, mc.rms_norm_eps, T, Hd, n, stream));
+    }
     if (mc.use_bias) {
         // Qwen3Config::use_bias (A-30): candle's Linear is matmul, then broadcast_add — two roundings —, and the row-parallel bias is added on
         // rank 0 BEFORE the all-reduce (linear.rs:206, :228-239): the GEMM keeps its plain epilogue and the bias is a launch of its own
@@ -850,6 +883,7 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
     if (f32) return forward_f32(T, B, is_prefill, max_ctx);
     if (is_prefill && tp_overlap == 2 && mb_rows > 0) return forward_prefill_two(T, B);
     const bool tl = tiled_weights && T <= 64;                            // decode-sized steps stream the tiled weight copies
+    const bool f8 = w_fp8 && tl;                                         // ... or the e4m3 bytes the *_t copies hold then (kernels/linear_fp8.hip)
     const int32_t *pslots = kv_fp8 ? no_slots : slots;                   // fp8 cache: the projection launches store no cache row (kv_store_fp8 below)
     const bool embed_norm = L > 0 && KD(embedding_rmsnorm_ok(T, Hd));                    // decode-sized: K1 + the first norm in one launch
     if (embed_norm) RC(KD(embedding_rmsnorm(ids, T, embed, layers[0].ln1, mc.rms_norm_eps, Hd, h, n, st)));
@@ -857,7 +891,10 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
     for (int64_t l = 0; l < L; ++l) {
         const Layer &w = layers[l];
         if (l == 0 && !embed_norm) RC(KD(rmsnorm(h, w.ln1, mc.rms_norm_eps, T, Hd, n, st)));   // later layers: see down_proj
-        if (mc.qk_norm || mc.use_bias) {         // A-27: the head norms sit between the projection and RoPE: plain GEMM, then one
+        if (f8) {                                // the byte stream has the plain epilogue: RoPE (+ head norms) and the KV store are a launch of their own
+            RC(KD(linear_fp8(n, Hd, reinterpret_cast<const uint8_t *>(w.qkv_t), w.qkv_s, T, Hd, QKV, qkv, st)));
+            RC(KD(rope_store_kv(qkv, pos, pslots, T, H, KVH, D, cos_t, sin_t, k_cache(l), v_cache(l), st, w.q_norm, w.k_norm, mc.rms_norm_eps)));
+        } else if (mc.qk_norm || mc.use_bias) {  // A-27: the head norms sit between the projection and RoPE: plain GEMM, then one
             RC(KD(linear(n, Hd, w.qkv, T, Hd, QKV, qkv, false, st, tl ? w.qkv_t : nullptr)));      // norm + RoPE + KV-store launch
             if (mc.use_bias) RC(KD(add_bias(qkv, w.qkv_b, T, QKV, st)));                            // A-30: the bias precedes the norms and RoPE (qwen3.rs:208-222)
             RC(KD(rope_store_kv(qkv, pos, pslots, T, H, KVH, D, cos_t, sin_t, k_cache(l), v_cache(l), st, w.q_norm, w.k_norm, mc.rms_norm_eps)));
@@ -915,6 +952,12 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
                 a.shared_count = (const int32_t *)(in_dev + off_dec + dof_scount);
             }
             RC(KD(attention(a, true, st)));
+        }
+        if (f8) {
+            RC(row_parallel_norm(attn, H * D, w.o, w.o_t, T, w.ln2, nullptr, w.o_s));
+            RC(KD(linear_silu_mul_fp8(n, Hd, reinterpret_cast<const uint8_t *>(w.gate_up_t), w.gate_up_s, T, Hd, I, act, st)));
+            RC(row_parallel_norm(act, I, w.down, w.down_t, T, l + 1 < L ? layers[l + 1].ln1 : norm, nullptr, w.down_s));
+            continue;
         }
         RC(row_parallel_norm(attn, H * D, w.o, tl ? w.o_t : nullptr, T, w.ln2, w.o_b));  // o_proj, residual :382, norm :385
         if (mc.use_bias) {                       // A-30: gate_up_proj, its bias, then SiluAndMul on the biased halves (qwen3.rs:305-314)

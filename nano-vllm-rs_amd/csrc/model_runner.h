@@ -39,6 +39,7 @@ struct nvr_model_runner {
 
     struct Layer { uint16_t *qkv, *o, *gate_up, *down, *ln1, *ln2;
                    uint16_t *qkv_t, *o_t, *gate_up_t, *down_t;      // *_t: tiled copies for the decode kernels (retile_weight), or null
+                   float *qkv_s, *o_s, *gate_up_s, *down_s;         // w_fp8: the *_t copies hold e4m3 BYTES and these the f32 scale of every output row, else null
                    uint16_t *q_norm, *k_norm;                       // mc.qk_norm: [D] each (ones until loaded), else null
                    uint16_t *qkv_b, *o_b, *gate_up_b, *down_b; };   // mc.use_bias: [QKV] / [Hd] (rank 0, else null) / [2I] / [Hd] (rank 0), else null
     std::vector<Layer> layers;
@@ -46,6 +47,10 @@ struct nvr_model_runner {
     uint16_t *lm_head_t = nullptr;         // tiled copy of the LM head (decode-sized steps)
     bool tiled_weights = true, tiled_dirty = true;   // env.tiled_weights = false keeps the row-major parameters only
     int retile_all();                      // (re)build the tiled copies from the row-major parameters (init, after load_tensor)
+    // nvr_config.decode_weight_dtype = "fp8": the decode copies of the four projection weights are e4m3 bytes + row scales (kernels/linear_fp8.hip) instead
+    // of tiled 16-bit copies; retile_all() quantises and overwrites the row-major weights with their dequantised values, so steps of > 64 rows (the 16-bit
+    // GEMMs over the row-major weights) and steps of <= 64 rows (the byte stream) compute with ONE set of weight values
+    bool w_fp8 = false;
     float *cos_t = nullptr, *sin_t = nullptr;
     uint16_t *kv_pool = nullptr;
     size_t kv_layer_elems = 0;             // elements of one K (or V) cache of one layer
@@ -151,7 +156,8 @@ private:
     float *f32_h2 = nullptr;                             // float32, one rank: second residual-stream buffer [8][hidden] of the decode-sized steps whose add + norm
                                                          // rides on the consumer GEMV (the workgroups of that launch still read the first while one of them writes)
     float *f32_gather = nullptr; int64_t f32_gather_rows = 0;   // float32 tensor-parallel ranks: every rank's partial sums [tp][f32_gather_rows][hidden], a piece of the step's rows at a time
-    int row_parallel_norm(const uint16_t *x, int64_t K, const uint16_t *W, const uint16_t *Wt, int64_t T, const uint16_t *wn, const uint16_t *bias = nullptr);
+    int row_parallel_norm(const uint16_t *x, int64_t K, const uint16_t *W, const uint16_t *Wt, int64_t T, const uint16_t *wn, const uint16_t *bias = nullptr,
+                          const float *w_scales = nullptr);      // w_scales (w_fp8, T <= 64): Wt holds bytes
     int64_t *h_tok_dev = nullptr;                        // device-visible address of the pinned token buffer h_tok
     int64_t slab_rows = 64;           // rows the split-k slab buffers hold (row_parallel_norm)
     // sharing group of a decode batch (0 = none / too small: plain paged attention); fills kv0[nseq], rows[nseq], *count of the arena

@@ -203,6 +203,7 @@ int nvr_runner_kv_cache(nvr_model_runner_t *r, size_t layer, void **kd, void **v
     return NVR_OK;
 }
 const char *nvr_runner_kv_cache_dtype(const nvr_model_runner_t *r) { return r->kv_fp8 ? "fp8_e4m3" : r->f32 ? "float32" : r->bf16 ? "bfloat16" : "float16"; }
+const char *nvr_runner_decode_weight_dtype(const nvr_model_runner_t *r) { return r->w_fp8 ? "fp8_e4m3" : r->f32 ? "float32" : r->bf16 ? "bfloat16" : "float16"; }
 int nvr_runner_set_kv_scales(nvr_model_runner_t *r, float k_scale, float v_scale) {
     if (!r->kv_fp8) return nvr::fail(NVR_ERR_UNSUPPORTED, "nvr_runner_set_kv_scales: the runner's KV cache is %s, not fp8", nvr_runner_kv_cache_dtype(r));
     if (!(k_scale > 0.f) || !(v_scale > 0.f) || std::isinf(k_scale) || std::isinf(v_scale))
@@ -549,6 +550,25 @@ int nvr_linear_silu_mul_tiled(const nvr_half *x, int64_t ldx, const nvr_half *W,
                               nvr_half *out, void *s) {
     NO_F32("nvr_linear_silu_mul_tiled");
     return KO(linear_silu_mul(x, ldx, W, T, K, I, out, (hipStream_t)s, Wt));
+}
+int nvr_weight_quantize_fp8(const nvr_half *W, int64_t N, int64_t K, uint8_t *Wq, float *scales, nvr_half *Wd, void *s) {
+    NO_F32("nvr_weight_quantize_fp8");
+    if (!W || !Wq || !scales) return nvr::fail(NVR_ERR_INVALID_ARG, "nvr_weight_quantize_fp8: null pointer");
+    return KO(weight_quantize_fp8(W, N, K, Wq, scales, Wd, (hipStream_t)s));
+}
+int nvr_linear_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, nvr_half *y, void *s) {
+    NO_F32("nvr_linear_fp8");
+    return KO(linear_fp8(x, ldx, Wq, scales, T, K, N, y, (hipStream_t)s));
+}
+int nvr_linear_silu_mul_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t I, nvr_half *out,
+                            void *s) {
+    NO_F32("nvr_linear_silu_mul_fp8");
+    return KO(linear_silu_mul_fp8(x, ldx, Wq, scales, T, K, I, out, (hipStream_t)s));
+}
+int nvr_linear_splitk_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, int64_t S,
+                          float *slabs, void *s) {
+    NO_F32("nvr_linear_splitk_fp8");
+    return KO(linear_splitk_fp8(x, ldx, Wq, scales, T, K, N, S, slabs, (hipStream_t)s));
 }
 int nvr_linear_qkv_rope_store_tiled(const nvr_half *x, int64_t ldx, const nvr_half *W, const nvr_half *Wt, int64_t T, int64_t K, int64_t H,
                                     int64_t KVH, int64_t D, const int64_t *pos, const int32_t *slots, const float *c, const float *sn,
