@@ -136,8 +136,9 @@ typedef struct nvr_config {
                                           where the same prompt served whole sees its projections; decode always sees the bytes.  It needs a 16-bit dtype,
                                           head_dim 64 / 128 and 1, 2 or 4 query heads per kv head, and for recompute_cached_prefix = 0 or
                                           enable_chunked_prefill = 1 a kvcache_block_size that is a power of two >= 64 (NVR_ERR_UNSUPPORTED otherwise); with
-                                          such a block size it takes the shared-prefix decode launch (nvr_paged_attn_decode_shared_fp8), it never takes the
-                                          work-balanced one.  Anything else: NVR_ERR_INVALID_ARG ("Unsupported kv_cache_dtype: ...") */
+                                          such a block size it takes the shared-prefix decode launch (nvr_paged_attn_decode_shared_fp8); with a block size
+                                          that is a power of two >= 16 (head_dim 128) / 32 (head_dim 64) its ragged decode batches take the work-balanced
+                                          launch (nvr_runner_last_decode_ragged; NVR_ATTN_SHARE=0 when the runner is created: never).  Anything else: NVR_ERR_INVALID_ARG ("Unsupported kv_cache_dtype: ...") */
     char decode_weight_dtype[16];      /* extension (the reference streams 16-bit weights): "" | "auto" (default): nothing changes, bit for bit; "fp8" |
                                           "fp8_e4m3": steps of <= 64 rows stream the four projection weights of every layer as OCP e4m3 bytes with one
                                           power-of-two f32 scale per output row (nvr_weight_quantize_fp8 / nvr_linear_fp8, nvr_linear_silu_mul_fp8,
@@ -632,8 +633,12 @@ NVR_API int nvr_kv_store_fp8(const nvr_half *qkv, const int32_t *slot_mapping, i
 /* K9 over such caches (attention.rs:225-235,264-318, A-8: the semantics of nvr_paged_attn_decode with K = k_scale * bytes, V = v_scale * bytes;
  * k_scale is folded into the softmax scale, v_scale multiplies the finished row).  D in {64, 128}, H / KVH in {1, 2, 4}, block_size at least one
  * row group of the kernel (8 rows at D = 128, 16 at D = 64); other shapes and "float32": NVR_ERR_UNSUPPORTED.  workspace:
- * nvr_paged_attn_workspace_bytes.  tickets: accepted for symmetry with nvr_paged_attn_decode_fused and not used (split contexts are
- * merged by a second launch); may be NULL. */
+ * nvr_paged_attn_workspace_bytes.  tickets: [B * KVH] device words, ZERO before the first call and owned by these calls afterwards (the kernel
+ * re-arms them; one call at a time per array), or NULL.  With tickets, a block_size that is a power of two >= 16 (D = 128) / 32 (D = 64) and a
+ * pair count that fills rounds of one workgroup per (sequence, kv head) badly (more pairs than CUs, >= 15 % of the rounds' slots empty, contexts
+ * of >= 256 keys) the call takes the work-balanced launch: one workgroup per CU walks an equal share of all pairs' keys and the last share of a
+ * cut pair to finish merges the pair's partials (NVR_ATTN_SHARE=0: never).  Without tickets: the per-pair launches, split contexts merged by a
+ * second launch. */
 NVR_API int nvr_paged_attn_decode_fp8(const nvr_half *q, int64_t ldq, const uint8_t *k_cache, const uint8_t *v_cache,
                                       const nvr_attn_meta *meta, int64_t H, int64_t KVH, int64_t D, int64_t block_size,
                                       float scale, float k_scale, float v_scale, nvr_half *out, void *workspace,

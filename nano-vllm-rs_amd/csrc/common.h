@@ -22,6 +22,7 @@ struct Env {
     bool tp_graph = true;         // NVR_TP_GRAPH=0       tensor-parallel decode steps run eagerly
     bool f32_fused_norm = true;   // NVR_F32_FUSED_NORM=0 float32 decode-sized steps keep the add + RMSNorm launch in front of their GEMVs (bit-identical; A/B, tests)
     bool attn_fused_merge = true; // NVR_ATTN_FUSED_MERGE=0 split-KV decode attention keeps its merge launch (bit-identical; A/B, tests)
+    int attn_share = 1;           // NVR_ATTN_SHARE=0|2   0: an fp8-KV runner keeps the per-pair decode attention launch for ragged batches (A/B, tests); the kernels' launch rule reads the same switch
     int max_graphs = 256;         // NVR_MAX_GRAPHS=n     captured decode graphs kept before the cache is flushed (test hook)
     int p2p_timeout_ms = 20000;   // NVR_P2P_TIMEOUT_MS=n how long a peer-to-peer collective waits for a peer before it gives up
     bool p2p_fenced = false;      // NVR_P2P_FENCED=1     the one-shot collectives keep r04's release / acquire fences (kernels/comm_p2p.hip; nvr_runner_p2p_set_fenced)

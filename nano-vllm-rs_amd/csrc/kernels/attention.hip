@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "device_utils.h"
 #include "attn_merge.h"
+#include "attn_share.h"
 #include "../common.h"
 
 namespace nvr { namespace NVR_DT_NS {
@@ -635,12 +636,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_share_kernel(AttnParams p, in
 }
 
 // ---- launch configuration ------------------------------------------------------------------------
-static int share_mode() { static const int v = getenv("NVR_ATTN_SHARE") ? atoi(getenv("NVR_ATTN_SHARE")) : 1; return v; }   // 0: never, 1: by the rule, 2: whenever it can run (probes)
-static bool share_enabled() { return share_mode() != 0; }
-static int share_workgroups() {                                           // one workgroup per CU of the current device
-    static const int v = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256; return n; }();
-    return v;
-}
+// (share_mode / share_enabled / share_workgroups: attn_share.h, shared with attention_fp8.hip)
 static inline int parts_for(int64_t nq, int64_t KVH, int64_t max_ctx, int waves, int *part_size) {
     // aim at ~4096 waves over the 256 CUs; partitions are multiples of 64 tokens
     const int64_t want_wgs = 4096 / waves;

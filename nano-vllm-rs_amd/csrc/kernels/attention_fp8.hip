@@ -13,11 +13,15 @@
 // back to back before any arithmetic.  Dequantisation is in registers: K bytes -> packed 16-bit pairs (v_cvt_scalef32_pk_f16_fp8 /
 // _bf16_fp8, scale operand 1.0) -> v_dot2 against the q pairs; V bytes -> f32 pairs (v_cvt_pk_f32_fp8) -> f32 FMA.  The butterfly of a
 // row's dot product runs over D/16 lanes and the 64/(D/16) row-group slots of a wave are merged once, at the end.
+//
+// Two launches: one or more workgroups per (query, kv head) pair (attn_fp8_kernel, + attn_fp8_merge_kernel for split contexts), or — pair counts that fill the
+// per-pair rounds badly, ragged batches — workgroups that walk equal shares of all pairs' keys (attn_share_fp8_kernel).
 #include <algorithm>
 #include <type_traits>
 #include "kernels.h"
 #include "device_utils.h"
 #include "attn_merge.h"
+#include "attn_share.h"
 #include "../common.h"
 
 namespace nvr { namespace NVR_DT_NS {
@@ -356,6 +360,266 @@ __global__ __launch_bounds__(256) void attn_fp8_merge_kernel(const float *__rest
     *reinterpret_cast<half4_t *>(out + pair * D + d) = hv;
 }
 
+// ---- work-balanced form ------------------------------------------------------------------------------------------------------------
+// The byte-cache counterpart of attention.hip's attn_share_kernel, in the geometry of attn_fp8_kernel above.  The launch is nw workgroups of WAVES waves and the
+// WORK is cut evenly: the keys of all (query, kv head) pairs, in units of CH = WAVES * TPI keys (one full round of a workgroup: 128 keys at D = 128, 256 at D = 64,
+// i.e. 16 KiB of K and of V either way), pair after pair (query-major), form one line of U_tot units; workgroup w walks the units [w * U_tot / nw, (w + 1) * U_tot / nw)
+// — a suffix of one pair, whole pairs, a prefix of another: a SEGMENT each.  A pair inside one share is written directly as 16-bit rows; a pair cut by share
+// boundaries leaves one f32 partial per share (v_scale applied; slot = share index - first share of the pair) and the LAST of its shares to take the pair's ticket
+// merges them in slot order (merge_partitions) and re-arms the counter.  The next segment is OPENED under the tail of the one in front: its query slice, its
+// block-table chunk and its first K / V requests are issued before the current segment's cross-wave merge.  Block size: a power of two >= TPI, so a chunk lies in
+// one cache block and its block-table entry is a v_readlane from the 64-entry register copy (reloaded when the walk crosses into the next 64 entries).
+// Registers: 119 VGPRs at G = 1, 151-153 at G = 2, 219-220 at G = 4, no scratch: from G = 2 on ONE workgroup is resident per CU (the per-pair kernel: two).
+// Holding G = 2 to 128 VGPRs (amdgpu_waves_per_eu) spills 104-132 bytes per lane and loses: profiles/fp8_ragged.txt.
+template <int D, int G, int U, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void attn_share_fp8_kernel(AttnFp8Params p, unsigned int *tickets, int nq, int nw) {
+    constexpr int LPR = D / 16, RPI = 64 / LPR, TPI = RPI * U, CH = TPI * WAVES;
+    static_assert(G * D <= WAVES * 64 && G * (D / 4) <= WAVES * 64, "one pass over the (head, column) pairs");
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int dc = lane % LPR, tg = lane / LPR;
+    __shared__ int pre[1025];                               // pre[t] = units of the queries in front of t (a query's KVH pairs have the same count)
+    __shared__ int cx[1024];                                // ctx_lens[t]
+    __shared__ float sm_acc[WAVES][G][D];
+    __shared__ float sm_ml[WAVES][G][2];
+    __shared__ unsigned int ticket_s;
+    if (wave == 0) {
+        int base = 0;
+        for (int k = 0; k < nq; k += 64) {
+            const int t = k + lane;
+            const int c = t < nq ? p.ctx_lens[t] : 0;
+            int un = (c + CH - 1) / CH;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(un, o, 64); if (lane >= o) un += v; }
+            if (t < nq) { pre[t + 1] = base + un; cx[t] = c; }
+            base += __shfl(un, 63, 64);
+        }
+        if (lane == 0) pre[0] = 0;
+    }
+    __syncthreads();
+    const long long utot = (long long)p.KVH * pre[nq];
+    const long long ub = (long long)blockIdx.x * utot / nw, ue = (long long)(blockIdx.x + 1) * utot / nw;
+    // a query without keys owns no unit: its output row is zero, as in attn_fp8_kernel (L == 0)
+    for (int t0 = blockIdx.x; t0 < nq; t0 += nw)
+        if (cx[t0] == 0)
+            for (int x = threadIdx.x; x < p.H * D; x += WAVES * 64) p.out[(int64_t)t0 * p.H * D + x] = (half_t)0.f;
+    if (ub >= ue) return;                                   // (fewer units than workgroups: an empty share)
+    const int row_bytes = p.KVH * D;
+
+    // ---- state of the segment being streamed (set by `open`, which also REQUESTS its first K / V rows) ----
+    int t = 0, g = 0, np = 1, slot = 0, p0 = 0, pend = 0, R = 0, ng = 0, gt0 = 0, bt_chunk = -1, bt_reg = 0;
+    const int32_t *bt = p.block_tables;
+    half2_t qv[G][8];
+    uint4_t k0[U], v0[U], kt[U], vt[U];                     // round 0 of the segment; its remainder groups
+    auto load16 = [](const uint8_t *ptr) { return __builtin_nontemporal_load(reinterpret_cast<const uint4_t *>(ptr)); };
+    auto block_base = [&](int tb) -> int64_t {              // byte offset of (scalar token tb, kv head g, d = 0)
+        const int bi = tb >> p.bs_shift, bo = tb & (p.block_size - 1);
+        if ((bi >> 6) != bt_chunk) { bt_chunk = bi >> 6; const int idx = (bt_chunk << 6) + lane; bt_reg = idx < p.max_blocks ? bt[idx] : 0; }
+        const int blk = __builtin_amdgcn_readlane(bt_reg, bi & 63);
+        return (((int64_t)blk * p.block_size + bo) * p.KVH + g) * D;
+    };
+    auto issue_remainder = [&]() {
+#pragma unroll
+        for (int x = 0; x < U; ++x) {
+            const int gt = gt0 + x * WAVES;
+            if (gt < ng) {                                  // uniform
+                const int tb = p0 + gt * RPI;               // (rows past the segment's end repeat row pend - 1: a key of this context, masked by CHECK)
+                const int64_t base = block_base(tb);
+                const unsigned off = (unsigned)(min(tg, pend - 1 - tb) * row_bytes + dc * 16);
+                kt[x] = load16(p.k + base + off); vt[x] = load16(p.v + base + off);
+            } else {
+                kt[x] = (uint4_t){0u, 0u, 0u, 0u}; vt[x] = (uint4_t){0u, 0u, 0u, 0u};
+            }
+        }
+    };
+    auto load_round = [&](int r, uint4_t (&kk)[U], uint4_t (&vv)[U]) {
+        const int64_t base = block_base(p0 + (r * WAVES + wave) * TPI);
+#pragma unroll
+        for (int x = 0; x < U; ++x) {
+            const unsigned off = (unsigned)((x * RPI + tg) * row_bytes + dc * 16);
+            kk[x] = load16(p.k + base + off); vv[x] = load16(p.v + base + off);
+        }
+    };
+    // opens the segment that starts at unit u (u < ue); returns its length in units
+    auto open = [&](long long u) -> int {
+        int lo = 0, hi = nq;                                // the query of unit u: the last t with KVH * pre[t] <= u (queries without keys own no unit)
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((long long)p.KVH * pre[mid] <= u) lo = mid; else hi = mid; }
+        t = lo;
+        const int ut = pre[t + 1] - pre[t], rem = (int)(u - (long long)p.KVH * pre[t]);
+        g = rem / ut;
+        const int lu = rem - g * ut, seg = (int)min((long long)(ut - lu), ue - u);
+        // shares that touch this pair: unit x belongs to share floor(((x + 1) * nw - 1) / utot)
+        const long long S = (long long)p.KVH * pre[t] + (long long)g * ut, E = S + ut - 1;
+        const int wf = (int)(((S + 1) * nw - 1) / utot), wl = (int)(((E + 1) * nw - 1) / utot);
+        np = wl - wf + 1; slot = (int)blockIdx.x - wf;
+        p0 = lu * CH; pend = min(cx[t], (lu + seg) * CH);
+        ng = (pend - p0 + RPI - 1) / RPI; R = (pend - p0) / CH; gt0 = R * (WAVES * U) + wave;
+        bt = p.block_tables + (int64_t)t * p.max_blocks;
+        bt_chunk = (p0 >> p.bs_shift) >> 6;
+        { const int idx = (bt_chunk << 6) + lane; bt_reg = idx < p.max_blocks ? bt[idx] : 0; }
+        const half_t *qrow = p.q + (int64_t)t * p.ldq + (int64_t)g * G * D + dc * 16;
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const half8_t a = *reinterpret_cast<const half8_t *>(qrow + i * D), b = *reinterpret_cast<const half8_t *>(qrow + i * D + 8);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { qv[i][j] = (half2_t){a[2 * j], a[2 * j + 1]}; qv[i][4 + j] = (half2_t){b[2 * j], b[2 * j + 1]}; }
+        }
+        if (R >= 1) load_round(0, k0, v0);
+        if (R <= 1) issue_remainder();                      // (requested before the arithmetic of the last full round, as in attn_fp8_kernel)
+        asm volatile("" ::: "memory");                      // the requests stay HERE: hipcc would sink them to their first use, behind the tail of the segment in front
+        return seg;
+    };
+
+    long long u = ub;
+    u += open(u);
+    for (;;) {
+        // online softmax state per head AND per row-group slot of the wave (merged once, at the segment's end)
+        float m[G], l[G], acc[G][16];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            m[i] = -INFINITY; l[i] = 0.f;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[i][j] = 0.f;
+        }
+        // attn_fp8_kernel's arithmetic; CHECK: slot x holds token tok0 + x * WAVES * RPI + tg, valid < pend
+        auto process = [&](auto check, const uint4_t (&kk)[U], const uint4_t (&vv)[U], int tok0) {
+            constexpr bool CHECK = decltype(check)::value;
+            float s[U][G];
+#pragma unroll
+            for (int x = 0; x < U; ++x) {
+                const bool valid = !CHECK || tok0 + x * (WAVES * RPI) + tg < pend;
+                half2_t kh[8];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) fp8x4_to_half2(kk[x][j], kh[2 * j], kh[2 * j + 1]);
+#pragma unroll
+                for (int i = 0; i < G; ++i) {
+                    float d = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) d = dot2(kh[j], qv[i][j], d);
+                    d = byte_row_sum<LPR>(d);
+                    s[x][i] = valid ? d * p.scale : -INFINITY;               // (a NaN byte behind the context ends here)
+                }
+            }
+            float alpha[G], ms[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                float mx = s[0][i];
+#pragma unroll
+                for (int x = 1; x < U; ++x) mx = fmaxf(mx, s[x][i]);
+                const float mn = fmaxf(m[i], mx);
+                ms[i] = (CHECK && mn == -INFINITY) ? 0.f : mn;               // a slot that has seen no valid token yet
+                alpha[i] = __expf(m[i] - ms[i]);
+                m[i] = mn;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[i][j] *= alpha[i];
+            }
+            float ps[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) ps[i] = 0.f;
+#pragma unroll
+            for (int x = 0; x < U; ++x) {
+                float vf[16];                                                // the row's V bytes once for all G heads (rows >= pend repeat row pend - 1 with p = 0)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float2_t a = __builtin_amdgcn_cvt_pk_f32_fp8(vv[x][j], false), b = __builtin_amdgcn_cvt_pk_f32_fp8(vv[x][j], true);
+                    vf[4 * j] = a[0]; vf[4 * j + 1] = a[1]; vf[4 * j + 2] = b[0]; vf[4 * j + 3] = b[1];
+                }
+#pragma unroll
+                for (int i = 0; i < G; ++i) {
+                    const float pr = __expf(s[x][i] - ms[i]);
+                    ps[i] += pr;
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) acc[i][j] = fmaf(pr, vf[j], acc[i][j]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < G; ++i) l[i] = __fmaf_rn(l[i], alpha[i], ps[i]);
+        };
+        if (R >= 1) process(std::false_type{}, k0, v0, 0);
+        for (int r = 1; r < R; ++r) {
+            uint4_t kk[U], vv[U];
+            load_round(r, kk, vv);
+            if (r == R - 1) issue_remainder();
+            process(std::false_type{}, kk, vv, 0);
+        }
+        if (gt0 < ng) process(std::true_type{}, kt, vt, p0 + gt0 * RPI);
+
+        // the segment is in the accumulators: what its tail needs of the state, then the NEXT segment is opened (its query, block table and first K / V rows
+        // are on their way while this one is merged and handed over)
+        const int st = t, sg = g, snp = np, sslot = slot;
+        const bool more = u < ue;
+        if (more) u += open(u);
+
+        // row-group slots of the wave -> the wave's sums; waves -> the segment's partial (attn_fp8_kernel's arithmetic)
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const float M = slots_max<LPR>(m[i]);
+            const float w = (m[i] == -INFINITY) ? 0.f : __expf(m[i] - M);
+            l[i] = slots_sum<LPR>(l[i] * w);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[i][j] = slots_sum<LPR>(acc[i][j] * w);
+            if (tg == 0) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) sm_acc[wave][i][dc * 16 + j] = acc[i][j];
+                if (dc == 0) { sm_ml[wave][i][0] = M; sm_ml[wave][i][1] = l[i]; }
+            }
+        }
+        __syncthreads();
+        const int64_t pair0 = ((int64_t)st * p.H + (int64_t)sg * G) * p.num_parts;
+        const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(p.part_o + pair0 * D, 0, (int)(G * p.num_parts * D * 4), 0x00020000);
+        const auto rs_ml = __builtin_amdgcn_make_buffer_rsrc(p.part_ml + pair0 * 2, 0, (int)(G * p.num_parts * 2 * 4), 0x00020000);
+        if (threadIdx.x < G * D) {
+            const int i = threadIdx.x / D, d = threadIdx.x % D;
+            float M = sm_ml[0][i][0];
+#pragma unroll
+            for (int w2 = 1; w2 < WAVES; ++w2) M = fmaxf(M, sm_ml[w2][i][0]);
+            float o = 0.f, L = 0.f;
+#pragma unroll
+            for (int w2 = 0; w2 < WAVES; ++w2) {
+                const float mw = sm_ml[w2][i][0];
+                const float wgt = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+                o = fmaf(wgt, sm_acc[w2][i][d], o);
+                L = fmaf(wgt, sm_ml[w2][i][1], L);
+            }
+            o *= p.v_scale;                                                   // once per segment: in front of the division, or of the (linear) merge of the partials
+            if (snp == 1) {
+                p.out[((int64_t)st * p.H + sg * G + i) * D + d] = (half_t)(L > 0.f ? o / L : 0.f);
+            } else {
+                const int sl = i * p.num_parts + sslot;
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), rs_o, (sl * D + d) * 4, 0, 16);
+                if (d == 0) { __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(M), rs_ml, sl * 8, 0, 16);
+                              __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(L), rs_ml, sl * 8 + 4, 0, 16); }
+            }
+        }
+        if (snp > 1) {                                                        // (workgroup-uniform)
+            constexpr int TPH = D / 4;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // every storing wave drains its stores (and the next segment's first rows land) ...
+            __syncthreads();
+            unsigned int *cnt = tickets + (int64_t)st * p.KVH + sg;
+            if (threadIdx.x == 0) ticket_s = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... one ticket
+            __syncthreads();
+            if (ticket_s == (unsigned)(snp - 1)) {                            // the last of the pair's shares to finish merges it
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");        // keeps the sc1 loads below the ticket
+                if (threadIdx.x < G * TPH) {
+                    const int i = threadIdx.x / TPH, d = (threadIdx.x % TPH) * 4;
+                    const half4_t hv = merge_partitions(snp,
+                        [&](int pi) { return __builtin_bit_cast(float2_t, __builtin_amdgcn_raw_buffer_load_b64(rs_ml, (i * p.num_parts + pi) * 8, 0, 16)); },
+                        [&](int pi) { return __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rs_o, ((i * p.num_parts + pi) * D + d) * 4, 0, 16)); });
+                    *reinterpret_cast<half4_t *>(p.out + ((int64_t)st * p.H + sg * G + i) * D + d) = hv;
+                }
+                if (threadIdx.x == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm for the next launch
+            }
+        }
+        if (!more) break;
+        __syncthreads();                                                      // sm_acc / sm_ml / ticket_s are the next segment's too
+    }
+}
+
+// block sizes the work-balanced form takes: a power of two >= the chunk of its U = 2 (16 keys at D = 128, 32 at D = 64)
+constexpr int SHARE_U = 2;
+bool attn_share_fp8_ok(int D, int block_size) {
+    return (D == 64 || D == 128) && block_size > 0 && (block_size & (block_size - 1)) == 0 && block_size >= 64 / (D / 16) * SHARE_U;
+}
+
 template <int D, int G, int WAVES>
 static void launch_fp8_cfg(const AttnFp8Params &p, int64_t nwg, hipStream_t s) {
     constexpr int U = 2, TPI = 64 / (D / 16) * U;                        // 2 KiB of K and of V in flight per wave: 16 tokens at D = 128, 32 at D = 64
@@ -407,6 +671,27 @@ static int launch_attn_fp8(const AttnFp8Args &a, hipStream_t s) {
         ps = ((mc + want - 1) / want + 63) / 64 * 64;
         np = (int)((mc + ps - 1) / ps);
     }
+    // Work-balanced form (attn_share_fp8_kernel), under the 16-bit launch's rule (attention.hip): a pair count whose last round of one-workgroup-per-pair launches
+    // would be mostly empty (more pairs than CUs with >= 15 % of the rounds' slots unused, contexts long enough for the stream to matter), a caller's balance_hint
+    // (a RAGGED batch: per-pair launches size every pair's partitions by the longest context), or NVR_ATTN_SHARE=2.  NVR_ATTN_SHARE=0: off.
+    if constexpr (G * D <= 512)
+    if (a.shared_len <= 0 && a.workspace && a.tickets && waves == 8 && attn_share_fp8_ok(D, a.block_size) && a.nq <= 1024 && share_enabled()) {
+        constexpr int CH = 8 * 64 / (D / 16) * SHARE_U;                   // keys of a unit
+        const int64_t cus = share_workgroups(), rounds = (pairs + cus - 1) / cus;
+        const int64_t most = (mc + CH - 1) / CH;                          // a pair has at most this many units, so it meets at most this many shares
+        const int64_t cap = a.workspace_bytes ? (int64_t)(a.workspace_bytes / ((size_t)a.nq * a.H * (D + 2) * sizeof(float))) : most;
+        const bool by_count = pairs > cus && rounds * cus * 100 >= pairs * 115 && mc >= 256;
+        // shares: one per CU for the pair-count case; for ragged batches the caller's count; probes: two per CU, three from 2 pairs per CU on
+        const int64_t nw = a.balance_hint > 0 ? a.balance_hint : share_mode() == 2 ? cus * (pairs <= 2 * cus ? 2 : 3) : cus;
+        if ((by_count || a.balance_hint > 0 || share_mode() == 2) && pairs < 2048 && cap >= most) {
+            p.part_size = CH; p.num_parts = (int32_t)most;                // slots per (query, head): [nq, H, most, D] and [nq, H, most, 2]
+            p.part_o = (float *)a.workspace; p.part_ml = p.part_o + (int64_t)a.nq * a.H * most * D;
+            attn_share_fp8_kernel<D, G, SHARE_U, 8><<<dim3((unsigned)nw), dim3(512), 0, s>>>(p, a.tickets, (int)a.nq, (int)nw);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "attention_fp8 (work-balanced) launch failed: %s", hipGetErrorString(e));
+            return 0;
+        }
+    }
     if (np > 1) {
         const size_t need = (size_t)a.nq * a.H * np * (D + 2) * sizeof(float);
         if (a.workspace_bytes && need > a.workspace_bytes)
@@ -436,7 +721,6 @@ static int launch_attn_fp8(const AttnFp8Args &a, hipStream_t s) {
 int attention_fp8(const AttnFp8Args &a, hipStream_t s) {
     if (a.nq == 0) return 0;
     if (a.KVH <= 0 || a.H % a.KVH) return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: H=%d not a multiple of KVH=%d", a.H, a.KVH);
-    if (a.balance_hint > 0) return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: the work-balanced form exists for 16-bit caches only");
     if (!(a.k_scale > 0.f) || !(a.v_scale > 0.f)) return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: scales %g / %g (positive)", a.k_scale, a.v_scale);
     const int G = a.H / a.KVH;
     const bool shape_ok = (a.D == 64 || a.D == 128) && (G == 1 || G == 2 || G == 4);

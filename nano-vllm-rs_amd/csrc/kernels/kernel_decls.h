@@ -140,6 +140,8 @@ int attention(const AttnArgs &a, bool paged, hipStream_t s);
 int kv_store_fp8(const half_bits *qkv, const int32_t *slots, int64_t T, int64_t H, int64_t KVH, int64_t D, float k_scale, float v_scale,
                  uint8_t *k_cache, uint8_t *v_cache, hipStream_t s);
 int attention_fp8(const AttnFp8Args &a, hipStream_t s);
+// the work-balanced form of attention_fp8 can run: block_size a power of two >= the kernel's chunk (16 keys at D = 128, 32 at D = 64)
+bool attn_share_fp8_ok(int D, int block_size);
 
 bool flash_prefill_ok(int D, int H, int KVH);
 int flash_tile_positions(int H, int KVH);

@@ -171,6 +171,8 @@ int nvr_model_runner::init() {                                       // ModelRun
         NVR_HIP_CHECK(hipMalloc((void **)&attn_tickets, (size_t)(max_seqs * KVH) * sizeof(unsigned int)));
         NVR_HIP_CHECK(hipMemset(attn_tickets, 0, (size_t)(max_seqs * KVH) * sizeof(unsigned int)));
     }
+    // an fp8 runner's decode steps may take the work-balanced attention launch: the counters exist, the block size suits the kernel, NVR_ATTN_SHARE is not 0
+    share_fp8 = kv_fp8 && attn_tickets && env.attn_share != 0 && KD(attn_share_fp8_ok((int)D, (int)block_size));
     // step-input arena
     auto carve = [&](size_t &off, size_t bytes) { off = in_bytes; in_bytes += (bytes + 255) / 256 * 256; };
     // prefill region (the start of the arena): capacity for the largest step; a step lays its arrays out back to back for its own
@@ -784,6 +786,14 @@ bool nvr_model_runner::ragged_batch(size_t nseq, int64_t sum_ctx, int64_t max_ct
     // shares: two per CU (three from 2 pairs per CU on), but none of less than four units (a tensor-parallel rank with one kv head: 32 sequences of 256..8192
     // keys are 1176 units — 512 shares of 2.3 units lost 2-5 % to the per-pair launch)
     decode_shares = (int32_t)std::max<int64_t>(64, std::min<int64_t>(cus * (pairs <= 2 * cus ? 2 : 3), units / 4));
+    // byte caches (attn_share_fp8_kernel): a unit is 128 (head_dim 128) or 256 keys and a share of one or two of them is mostly segment changes, so the count has
+    // two levels only — one share per CU below sixteen 64-key units per CU, the 16-bit count from there on.  (Two levels: the count is an argument of a captured
+    // graph, and a replay whose sum of contexts has grown by a few keys walks the shares it was captured with — the bits of the eager step.)
+    if (kv_fp8) decode_shares = (int32_t)(units >= 16 * cus ? cus * 2 : cus);
+    // ... and only up to one pair per CU: the byte kernel has one workgroup resident per CU where the per-pair kernel has two, so from two pairs per CU on the
+    // dispatcher balances the per-pair workgroups better than the static cut does (profiles/fp8_ragged.txt: 64 sequences x 8 kv heads of 64..4096 keys 2.47 per-pair
+    // against 2.58 ms per step; 32 x 8 of 256..8192 keys 2.91 against 2.21)
+    if (kv_fp8 && pairs > cus) return false;
     // ... and not below six units per CU in all: the step is then launch-bound and the per-pair launch's shorter ramp wins (12 sequences of 20..1500 keys: 1.08
     // against 1.24 ms per step; 8 of 64..8192 keys — 2040 units — 1.65 -> 1.33 the other way)
     return pairs <= 1024 && max_ctx * (int64_t)nseq * 100 >= sum_ctx * 130 && units >= 6 * cus;
@@ -937,6 +947,7 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
             f.nq = (int32_t)T; f.H = (int32_t)H; f.KVH = (int32_t)KVH; f.D = (int32_t)D; f.scale = scale; f.k_scale = k_scale; f.v_scale = v_scale;
             f.max_ctx = (int32_t)max_ctx; f.out = attn; f.workspace = attn_ws; f.workspace_bytes = attn_ws_bytes;
             f.shared_len = (int32_t)decode_shared_len;
+            f.tickets = share_fp8 ? attn_tickets : nullptr; f.balance_hint = decode_ragged ? decode_shares : 0;
             if (decode_shared_len > 0 && decode_shared_rows < T) {     // a group inside the batch: per-row kv0, member rows, member count
                 f.shared_kv0 = (const int32_t *)(in_dev + off_dec + dof_skv0); f.shared_rows = (const int32_t *)(in_dev + off_dec + dof_srows);
                 f.shared_count = (const int32_t *)(in_dev + off_dec + dof_scount);
@@ -1167,8 +1178,8 @@ int nvr_model_runner::execute(nvr_seq *const *seqs, size_t nseq, bool is_prefill
         decode_shared_len = shared_prefix_plan(seqs, nseq, (int32_t *)(hd + dof_skv0), (int32_t *)(hd + dof_srows), (int32_t *)(hd + dof_scount),
                                                &decode_shared_rows);
         decode_ragged = ragged_batch(nseq, sum_ctx, (cfg.enforce_eager || graphs_disabled) ? max_ctx : (max_ctx + 255) / 256 * 256);
-        if (kv_fp8) {                                        // attention_fp8 has no work-balanced form, and its shared pass takes whole 64-key steps of one block
-            decode_ragged = false;
+        if (kv_fp8) {                                        // attention_fp8's work-balanced form takes some block sizes only, and its shared pass takes whole 64-key steps of one block
+            decode_ragged = decode_ragged && share_fp8;
             if (!KD(flash_prefill_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size))) { decode_shared_len = 0; decode_shared_rows = 0; }
         }
     }
@@ -1266,7 +1277,7 @@ int nvr_model_runner::execute_decode_ahead(nvr_seq *const *seqs, size_t nseq, in
                                            &decode_shared_rows);
     decode_ragged = ragged_batch(nseq, sum_ctx, (cfg.enforce_eager || graphs_disabled) ? max_ctx : (max_ctx + 255) / 256 * 256);
     if (kv_fp8) {
-        decode_ragged = false;
+        decode_ragged = decode_ragged && share_fp8;
         if (!KD(flash_prefill_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size))) { decode_shared_len = 0; decode_shared_rows = 0; }
     }
     NVR_HIP_CHECK(hipMemcpyAsync(in_dev + off_dec + dof_pos, hd + dof_pos, dof_bt + nseq * max_blocks_per_seq * 4 - dof_pos, hipMemcpyHostToDevice, stream));

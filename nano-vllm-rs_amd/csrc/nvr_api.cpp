@@ -681,11 +681,10 @@ int nvr_kv_store_fp8(const nvr_half *qkv, const int32_t *slots, int64_t T, int64
 int nvr_paged_attn_decode_fp8(const nvr_half *q, int64_t ldq, const uint8_t *kc, const uint8_t *vc, const nvr_attn_meta *m, int64_t H, int64_t KVH,
                               int64_t D, int64_t bs, float scale, float k_scale, float v_scale, nvr_half *out, void *ws, uint32_t *tickets, void *s) {
     if (g_ops_f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "nvr_paged_attn_decode_fp8: 16-bit queries and outputs (nvr_ops_set_dtype float16 | bfloat16)");
-    (void)tickets;
     k::AttnFp8Args a{};
     a.q = q; a.ldq = ldq; a.k = kc; a.v = vc; a.ctx_lens = m->context_lens; a.block_tables = m->block_tables; a.max_blocks = m->max_blocks;
     a.block_size = (int32_t)bs; a.nq = m->batch; a.H = (int32_t)H; a.KVH = (int32_t)KVH; a.D = (int32_t)D; a.scale = scale; a.k_scale = k_scale;
-    a.v_scale = v_scale; a.max_ctx = m->max_context_len; a.out = out; a.workspace = ws;
+    a.v_scale = v_scale; a.max_ctx = m->max_context_len; a.out = out; a.workspace = ws; a.tickets = tickets;
     return KO(attention_fp8(a, (hipStream_t)s));
 }
 int nvr_paged_attn_decode_shared_fp8(const nvr_half *q, int64_t ldq, const uint8_t *kc, const uint8_t *vc, const nvr_attn_meta *m, int64_t H, int64_t KVH,
