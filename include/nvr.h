@@ -145,8 +145,11 @@ typedef struct nvr_config {
                                           nvr_linear_splitk_fp8) — the byte copy REPLACES the tiled 16-bit copy (3 instead of 4 weight bytes per element), and the
                                           row-major weights are overwritten by their dequantised values at creation and after nvr_runner_load_tensor, so larger
                                           steps (prefill) compute with the same weight values through the 16-bit GEMMs and nvr_runner_copy_weight returns the
-                                          dequantised values.  Activations are not quantised; embedding and LM head stay 16-bit.  Independent of
-                                          kv_cache_dtype.  It needs a 16-bit dtype, no biases, tensor_parallel_size 1 and hidden, heads x head_dim and
+                                          dequantised values.  Activations are not quantised; embedding and LM head stay 16-bit.  "fp8_head": all of
+                                          "fp8", and the LM head of steps of <= 64 LM-head rows (one per sequence of the step) streams bytes too
+                                          (nvr_lm_head_fp8): bytes + row scales REPLACE the tiled 16-bit head, the row-major head — with
+                                          tie_word_embeddings the embedding — holds its dequantised values, and the local vocabulary must be a multiple
+                                          of 16.  Independent of kv_cache_dtype.  It needs a 16-bit dtype, no biases, tensor_parallel_size 1 and hidden, heads x head_dim and
                                           intermediate sizes that are multiples of 64 (NVR_ERR_UNSUPPORTED otherwise).  Anything else: NVR_ERR_INVALID_ARG
                                           ("Unsupported decode_weight_dtype: ...") */
 } nvr_config;
@@ -566,6 +569,12 @@ NVR_API int nvr_linear_silu_mul_fp8(const nvr_half *x, int64_t ldx, const uint8_
                                     nvr_half *out, void *stream);
 NVR_API int nvr_linear_splitk_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N,
                                   int64_t S, float *slabs, void *stream);
+/* The LM head over the same bytes and scales (kernels/lm_head_fp8.hip): logits[T][N] f32 = x * (scales[n] * e4m3(Wq[n][k]))^T for 1 <= T <= 64 (logits
+ * NULL: not stored) and the greedy arg-max partials of nvr_lm_head, part_val / part_idx [*nparts][T] with *nparts <= NVR_LM_HEAD_MAX_PARTS, finished by
+ * nvr_argmax_partials; the partials do not depend on whether logits are stored.  K % 64 == 0, N % 16 == 0, ldx % 8 == 0, N < 2^31; beyond 32 rows or
+ * 2048 columns N <= 262144.  Same error rules as nvr_linear_fp8 (null x / Wq / scales / part_val / part_idx / nparts: NVR_ERR_INVALID_ARG). */
+NVR_API int nvr_lm_head_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, float *logits,
+                            float *part_val, int32_t *part_idx, int32_t *nparts, void *stream);
 NVR_API int nvr_linear_qkv_rope_store_tiled(const nvr_half *x, int64_t ldx, const nvr_half *W, const nvr_half *Wt, int64_t T,
                                             int64_t K, int64_t H, int64_t KVH, int64_t D, const int64_t *positions,
                                             const int32_t *slot_mapping, const float *cos_t, const float *sin_t,

@@ -223,6 +223,7 @@ _SIGS = {
     "nvr_lm_head_tiled": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "nvr_weight_quantize_fp8": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "nvr_linear_fp8": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    "nvr_lm_head_fp8": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "nvr_linear_silu_mul_fp8": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "nvr_linear_splitk_fp8": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "nvr_retile_weight": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P]),
@@ -685,7 +686,8 @@ class ModelRunner:
         return lib().nvr_runner_kv_cache_dtype(self.h).decode()
 
     def decode_weight_dtype(self) -> str:
-        """What steps of <= 64 rows stream as projection weights: the runner's dtype, or "fp8_e4m3" (Config(decode_weight_dtype="fp8"))."""
+        """What steps of <= 64 rows stream as projection weights: the runner's dtype, "fp8_e4m3" (Config(decode_weight_dtype="fp8")) or, when the LM head
+        streams bytes too, "fp8_e4m3_head" (Config(decode_weight_dtype="fp8_head"))."""
         return lib().nvr_runner_decode_weight_dtype(self.h).decode()
 
     def set_kv_scales(self, k_scale: float, v_scale: float) -> None:

@@ -55,7 +55,7 @@ int nvr_config_validate(const nvr_config *c) {                       // config.r
         return nvr::fail(NVR_ERR_INVALID_ARG, "Unsupported dtype: %.15s", c->dtype);
     if (!cfg_str_in(c->kv_cache_dtype, sizeof c->kv_cache_dtype, {"", "auto", "fp8", "fp8_e4m3"}))
         return nvr::fail(NVR_ERR_INVALID_ARG, "Unsupported kv_cache_dtype: %.15s", c->kv_cache_dtype);
-    if (!cfg_str_in(c->decode_weight_dtype, sizeof c->decode_weight_dtype, {"", "auto", "fp8", "fp8_e4m3"}))
+    if (!cfg_str_in(c->decode_weight_dtype, sizeof c->decode_weight_dtype, {"", "auto", "fp8", "fp8_e4m3", "fp8_head"}))
         return nvr::fail(NVR_ERR_INVALID_ARG, "Unsupported decode_weight_dtype: %.15s", c->decode_weight_dtype);
     if (c->decode_chain != 0 && c->decode_chain != 6)
         return nvr::fail(NVR_ERR_INVALID_ARG, "decode_chain must be 0 (reserved; 6 = the same six-launch chain), got %u", c->decode_chain);

@@ -36,6 +36,17 @@ __device__ __forceinline__ float4_t mfma16(half8_t a, half8_t b, float4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 #endif
 }
+// 8 e4m3 bytes -> the 8 16-bit elements of an MFMA A fragment, exactly
+__device__ __forceinline__ half8_t fp8x8_to_half8(unsigned int w0, unsigned int w1) {
+#ifdef NVR_BF16
+    const half2_t a = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false)), b = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
+    const half2_t c = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false)), d = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
+#else
+    const half2_t a = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false)), b = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true));
+    const half2_t c = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false)), d = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true));
+#endif
+    return (half8_t){a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
 // c + a.x * b.x + a.y * b.y in f32 (v_dot2_f32_f16 / v_dot2c_f32_bf16)
 __device__ __forceinline__ float dot2(half2_t a, half2_t b, float c) {
 #ifdef NVR_BF16

@@ -98,6 +98,15 @@ int linear_silu_mul_fp8(const half_bits *x, int64_t ldx, const uint8_t *Wq, cons
 int linear_splitk_fp8(const half_bits *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, int64_t S, float *slabs,
                       hipStream_t s);
 
+// LM head of steps of <= 64 rows over the same bytes and scales (lm_head_fp8.hip): f32 logits (logits null: none) + the arg-max partials of lm_head
+// ([*nparts][T], *nparts = lm_head_fp8_parts(...) <= LM_HEAD_MAX_PARTS, a pure function of the shape; 0: unsupported), finished by argmax_partials.
+// K % 64 == 0, N % 16 == 0, ldx % 8 == 0, N < 2^31; beyond 32 rows or 2048 columns N <= 262144 (a wave keeps the accumulators of all its tiles)
+int lm_head_fp8_prepare();                                                  // LDS opt-in of every instance (call outside captures)
+bool lm_head_fp8_ok(int64_t T, int64_t K, int64_t N, int64_t ldx);
+int32_t lm_head_fp8_parts(int64_t T, int64_t K, int64_t N, int64_t ldx);
+int lm_head_fp8(const half_bits *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, float *logits, float *part_val,
+                int32_t *part_idx, int32_t *nparts, hipStream_t s);
+
 // LM head over more than 32 rows: the 128x128 kernel with the logits / arg-max epilogue (one partial per 128-column tile)
 bool gemm_tiled_splitk_ok(int64_t T, int64_t K, int64_t N, int64_t S, int64_t ldx);
 int gemm_tiled_splitk(const half_bits *x, int64_t ldx, const half_bits *W, int64_t T, int64_t K, int64_t N, int64_t S, float *slabs, hipStream_t s);

@@ -98,18 +98,6 @@ struct Fp8Gemm {
     void *out;                         // 16-bit [T, N], or f32 slabs [S][T, N]
 };
 
-// 8 e4m3 bytes -> the 8 16-bit elements of an MFMA A fragment, exactly
-__device__ __forceinline__ half8_t fp8x8_to_half8(unsigned int w0, unsigned int w1) {
-#ifdef NVR_BF16
-    const half2_t a = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false)), b = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
-    const half2_t c = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false)), d = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
-#else
-    const half2_t a = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false)), b = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true));
-    const half2_t c = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false)), d = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true));
-#endif
-    return (half8_t){a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-}
-
 template <int MT, int EPI>
 struct Fp8Shape {
     static constexpr int NTT = EPI == FEPI_SILU ? 2 : 1;                    // weight parts per tile (gate, up)

@@ -44,6 +44,7 @@ nvr_model_runner::~nvr_model_runner() {
     for (auto &l : layers) { hipFree(l.qkv); hipFree(l.o); hipFree(l.gate_up); hipFree(l.down); hipFree(l.ln1); hipFree(l.ln2);
                              void *ts[] = {l.qkv_t, l.o_t, l.gate_up_t, l.down_t, l.qkv_s, l.o_s, l.gate_up_s, l.down_s, l.q_norm, l.k_norm, l.qkv_b, l.o_b, l.gate_up_b, l.down_b}; for (void *t : ts) if (t) hipFree(t); }
     if (lm_head_t) hipFree(lm_head_t);
+    if (lm_head_s) hipFree(lm_head_s);
     void *ptrs[] = {embed, mc.tie_word_embeddings ? nullptr : lm_head, norm, cos_t, sin_t, kv_pool, h, n, qkv, attn,
                     proj, gu, act, nlast, logits, attn_ws, slabs, in_dev, d_tok, d_maxval, d_temp, d_topk, d_topp, d_keys,
                     sample_ws, d_gather_val, d_gather_idx, d_gather_logits, d_full_logits, sample_ws_full, d_lm_pval, d_lm_pidx, d_rec, d_gather_rec, f32_gather, f32_h2, no_slots};
@@ -66,7 +67,8 @@ int nvr_model_runner::init() {                                       // ModelRun
     kv_fp8 = std::strncmp(cfg.kv_cache_dtype, "fp8", 3) == 0;                     // "fp8" | "fp8_e4m3" (nvr_config_validate has seen the name)
     kv_elem_bytes = kv_fp8 ? 1 : f32 ? 4 : 2;
     if (kv_fp8 && f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8 needs dtype float16 or bfloat16 (the fp8 kernels quantise and read 16-bit rows)");
-    w_fp8 = std::strncmp(cfg.decode_weight_dtype, "fp8", 3) == 0;                 // "fp8" | "fp8_e4m3"
+    w_fp8 = std::strncmp(cfg.decode_weight_dtype, "fp8", 3) == 0;                 // "fp8" | "fp8_e4m3" | "fp8_head"
+    head_fp8 = std::strcmp(cfg.decode_weight_dtype, "fp8_head") == 0;
     if (w_fp8 && f32) return nvr::fail(NVR_ERR_UNSUPPORTED, "decode_weight_dtype fp8 needs dtype float16 or bfloat16 (the byte stream feeds the 16-bit MFMAs)");
     if (w_fp8 && cfg.tensor_parallel_size > 1)
         return nvr::fail(NVR_ERR_UNSUPPORTED, "decode_weight_dtype fp8 needs tensor_parallel_size 1 (got %lu): the row-parallel exchange paths read 16-bit projections",
@@ -119,6 +121,9 @@ int nvr_model_runner::init() {                                       // ModelRun
     if (w_fp8 && (!env.tiled_weights || Hd % 64 || (H * D) % 64 || I % 64 || D % 16))
         return nvr::fail(NVR_ERR_UNSUPPORTED, "decode_weight_dtype fp8 needs the decode weight copies (NVR_TILED_WEIGHTS) and hidden %ld, heads x head_dim %ld, intermediate "
                          "%ld that are multiples of 64", (long)Hd, (long)(H * D), (long)I);
+    if (head_fp8 && Vl % 16)
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "decode_weight_dtype fp8_head needs a local vocabulary that is a multiple of 16 (got %ld): the LM head's byte stream "
+                         "is cut into 16-row tiles", (long)Vl);
     RC(gen_weights());
 
     // RoPE tables (rotary_embedding.rs:74-119, A-14): computed on the host in f64 from the f32 angle,
@@ -157,6 +162,7 @@ int nvr_model_runner::init() {                                       // ModelRun
     comm.force = env.tp_force_comm; comm.timeout_ms = env.p2p_timeout_ms; comm.p2p_fenced = env.p2p_fenced;
     RC(KD(linear_stream_prepare()));
     if (w_fp8) RC(KD(linear_fp8_prepare()));
+    if (head_fp8) RC(KD(lm_head_fp8_prepare()));
     RC(KD(gemm_tiled_prepare()));
     lazy_logits = env.lazy_logits && !f32;
     {   // arg-max partials [parts][rows]: <= LM_HEAD_MAX_PARTS x 32 rows (lm_head_kernel), or one per 128 vocabulary columns x all rows
@@ -260,7 +266,8 @@ int nvr_model_runner::retile_all() {
         RC(KD(retile_weight(w.gate_up, w.gate_up_t, 2 * I, Hd, 0, 0, 0, 0, stream)));
         RC(KD(retile_weight(w.down, w.down_t, Hd, I, 0, 0, 0, 0, stream)));
     }
-    if (lm_head_t) RC(KD(retile_weight(lm_head, lm_head_t, Vl, Hd, 0, 0, 0, 0, stream)));
+    if (head_fp8) RC(KD(weight_quantize_fp8(lm_head, Vl, Hd, reinterpret_cast<uint8_t *>(lm_head_t), lm_head_s, lm_head, stream)));   // tied: the embedding rows too
+    else if (lm_head_t) RC(KD(retile_weight(lm_head, lm_head_t, Vl, Hd, 0, 0, 0, 0, stream)));
     NVR_HIP_CHECK(hipStreamSynchronize(stream));
     return NVR_OK;
 }
@@ -461,7 +468,8 @@ int nvr_model_runner::gen_weights() {
         RC(KD(fill_weight(lm_head, Vl, Hd, Hd, Hd, vocab_start, 0, nvr_weight_key_impl(mc.seed, TID_LM_HEAD), sc, stream)));
     }
     RC(dmalloc(&norm, Hd)); RC(KD(fill_const(norm, Hd, 1.0f, stream)));
-    if (tiled_weights && Vl % 16 == 0) RC(dmalloc(&lm_head_t, Vl * Hd));
+    if (head_fp8) { RC(dmalloc(&lm_head_t, Vl * Hd / 2)); RC(dmalloc(&lm_head_s, Vl)); }   // one byte per element and a scale per vocabulary row
+    else if (tiled_weights && Vl % 16 == 0) RC(dmalloc(&lm_head_t, Vl * Hd));
     NVR_HIP_CHECK(hipStreamSynchronize(stream));
     return retile_all();
 }
@@ -875,9 +883,7 @@ int nvr_model_runner::forward_prefill_two(int64_t T, int64_t B) {
     for (int m = 0; m < 2; ++m) { NVR_HIP_CHECK(hipStreamWaitEvent(st, ev_reduced[2 * m + 1], 0)); RC(post_part(L - 1, m)); }
     RC(KD(select_last_tokens(n, d_cu, B, Hd, nlast, st)));                                       // embed_head.rs:272-289
     if (lm_parts > 0) {
-        int32_t np = 0;
-        RC(KD(lm_head(nlast, Hd, lm_head, B, Hd, Vl, logits, d_lm_pval, d_lm_pidx, &np, st, want_logits, (tiled_weights && B <= 32) ? lm_head_t : nullptr)));
-        if (np != lm_parts) return nvr::fail(NVR_ERR_INVARIANT, "lm_head produced %d partials, planned %d", np, lm_parts);
+        RC(run_lm_head(nlast, B, want_logits, st));
     } else {
         RC(KD(linear(nlast, Hd, lm_head, B, Hd, Vl, logits, true, st)));
     }
@@ -986,9 +992,7 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
     const uint16_t *hl = n;
     if (is_prefill) { RC(KD(select_last_tokens(n, d_cu, B, Hd, nlast, st))); hl = nlast; }      // embed_head.rs:272-289
     if (lm_parts > 0) {                                                                        // f32 logits (A-21) + arg-max partials
-        int32_t np = 0;
-        RC(KD(lm_head(hl, Hd, lm_head, B, Hd, Vl, logits, d_lm_pval, d_lm_pidx, &np, st, want_logits, (tiled_weights && B <= 32) ? lm_head_t : nullptr)));
-        if (np != lm_parts) return nvr::fail(NVR_ERR_INVARIANT, "lm_head produced %d partials, planned %d", np, lm_parts);
+        RC(run_lm_head(hl, B, want_logits, st));
     } else {
         RC(KD(linear(hl, Hd, lm_head, B, Hd, Vl, logits, true, st)));
     }
@@ -1193,7 +1197,7 @@ int nvr_model_runner::execute(nvr_seq *const *seqs, size_t nseq, bool is_prefill
     last_rows = nseq; last_prefill = is_prefill; last_tokens = T;
     // arg-max partials come with the logits when the whole batch goes through one lm_head launch (a pure function of
     // the shapes, so a replayed graph and this bookkeeping always agree)
-    lm_parts = lm_fused ? KD(lm_head_parts((int64_t)nseq, Hd, Vl, Hd)) : 0;
+    lm_parts = lm_fused ? plan_lm_parts((int64_t)nseq) : 0;
     // a batch that samples greedily everywhere takes its tokens from the arg-max partials: the f32 logits are then written
     // only on demand (ensure_logits: execute_model callers that ask for them, copy_logits)
     want_logits = !lazy_logits || lm_parts == 0;
@@ -1282,7 +1286,7 @@ int nvr_model_runner::execute_decode_ahead(nvr_seq *const *seqs, size_t nseq, in
     }
     NVR_HIP_CHECK(hipMemcpyAsync(in_dev + off_dec + dof_pos, hd + dof_pos, dof_bt + nseq * max_blocks_per_seq * 4 - dof_pos, hipMemcpyHostToDevice, stream));
     last_rows = nseq; last_prefill = false; last_tokens = (int64_t)nseq;
-    lm_parts = KD(lm_head_parts((int64_t)nseq, Hd, Vl, Hd));
+    lm_parts = plan_lm_parts((int64_t)nseq);
     if (lm_parts <= 0) return nvr::fail(NVR_ERR_UNSUPPORTED, "execute_decode_ahead: the fused LM head does not take this batch");
     want_logits = !lazy_logits; logits_valid = want_logits; lm_input = n;
     const int64_t T = (int64_t)nseq;
@@ -1492,15 +1496,29 @@ int nvr_model_runner::comm_selftest() {
     return NVR_OK;
 }
 
+// The LM-head launch of a step and its plan.  "fp8_head" runners stream the head's bytes for every row count lm_head_fp8 takes (<= 64 rows); everything else,
+// and their larger steps, goes through the 16-bit kernels over the row-major head (there lm_head_t holds bytes, not the tiled 16-bit copy).
+int32_t nvr_model_runner::plan_lm_parts(int64_t rows) const {
+    if (head_fp8 && KD(lm_head_fp8_ok(rows, Hd, Vl, Hd))) return KD(lm_head_fp8_parts(rows, Hd, Vl, Hd));
+    return KD(lm_head_parts(rows, Hd, Vl, Hd));
+}
+int nvr_model_runner::run_lm_head(const uint16_t *x, int64_t rows, bool store_logits, hipStream_t st) {
+    int32_t np = 0;
+    if (head_fp8 && KD(lm_head_fp8_ok(rows, Hd, Vl, Hd)))
+        RC(KD(lm_head_fp8(x, Hd, reinterpret_cast<const uint8_t *>(lm_head_t), lm_head_s, rows, Hd, Vl, store_logits ? logits : nullptr, d_lm_pval, d_lm_pidx, &np, st)));
+    else
+        RC(KD(lm_head(x, Hd, lm_head, rows, Hd, Vl, logits, d_lm_pval, d_lm_pidx, &np, st, store_logits, (tiled_weights && !head_fp8 && rows <= 32) ? lm_head_t : nullptr)));
+    if (np != lm_parts) return nvr::fail(NVR_ERR_INVARIANT, "lm_head produced %d partials, planned %d", np, lm_parts);
+    return NVR_OK;
+}
+
 // sample_tokens :131-156 -> Sampler::batch_sample, src/layers/sampler.rs:221-254
 // the f32 logits of the last step, if that step skipped their stores: the LM-head launch is repeated on the same
 // (still resident) hidden rows with the stores on — same kernel, same bits
 int nvr_model_runner::ensure_logits() {
     if (logits_valid) return NVR_OK;
     NVR_HIP_CHECK(hipSetDevice(device));
-    int32_t np = 0;
-    RC(KD(lm_head(lm_input, Hd, lm_head, (int64_t)last_rows, Hd, Vl, logits, d_lm_pval, d_lm_pidx, &np, stream, true,
-                  (tiled_weights && last_rows <= 32) ? lm_head_t : nullptr)));
+    RC(run_lm_head(lm_input, (int64_t)last_rows, true, stream));
     logits_valid = true;
     return NVR_OK;
 }

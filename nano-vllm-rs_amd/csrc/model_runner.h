@@ -47,10 +47,16 @@ struct nvr_model_runner {
     uint16_t *lm_head_t = nullptr;         // tiled copy of the LM head (decode-sized steps)
     bool tiled_weights = true, tiled_dirty = true;   // env.tiled_weights = false keeps the row-major parameters only
     int retile_all();                      // (re)build the tiled copies from the row-major parameters (init, after load_tensor)
-    // nvr_config.decode_weight_dtype = "fp8": the decode copies of the four projection weights are e4m3 bytes + row scales (kernels/linear_fp8.hip) instead
+    // nvr_config.decode_weight_dtype = "fp8" / "fp8_head": the decode copies of the four projection weights are e4m3 bytes + row scales (kernels/linear_fp8.hip) instead
     // of tiled 16-bit copies; retile_all() quantises and overwrites the row-major weights with their dequantised values, so steps of > 64 rows (the 16-bit
     // GEMMs over the row-major weights) and steps of <= 64 rows (the byte stream) compute with ONE set of weight values
     bool w_fp8 = false;
+    // "fp8_head": in addition lm_head_t holds the e4m3 bytes of the LM head and lm_head_s its row scales (kernels/lm_head_fp8.hip) for steps of <= 64 LM-head
+    // rows; the row-major head (tied: the embedding) holds the dequantised values, which the gather and the 16-bit LM-head kernels of larger steps read
+    bool head_fp8 = false;
+    float *lm_head_s = nullptr;
+    int32_t plan_lm_parts(int64_t rows) const;                                          // partials run_lm_head will write for this many rows (0: unsupported)
+    int run_lm_head(const uint16_t *x, int64_t rows, bool store_logits, hipStream_t st);   // logits (on demand) + lm_parts partials, by the runner's head route
     float *cos_t = nullptr, *sin_t = nullptr;
     uint16_t *kv_pool = nullptr;
     size_t kv_layer_elems = 0;             // elements of one K (or V) cache of one layer

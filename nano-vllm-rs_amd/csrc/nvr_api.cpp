@@ -203,7 +203,7 @@ int nvr_runner_kv_cache(nvr_model_runner_t *r, size_t layer, void **kd, void **v
     return NVR_OK;
 }
 const char *nvr_runner_kv_cache_dtype(const nvr_model_runner_t *r) { return r->kv_fp8 ? "fp8_e4m3" : r->f32 ? "float32" : r->bf16 ? "bfloat16" : "float16"; }
-const char *nvr_runner_decode_weight_dtype(const nvr_model_runner_t *r) { return r->w_fp8 ? "fp8_e4m3" : r->f32 ? "float32" : r->bf16 ? "bfloat16" : "float16"; }
+const char *nvr_runner_decode_weight_dtype(const nvr_model_runner_t *r) { return r->head_fp8 ? "fp8_e4m3_head" : r->w_fp8 ? "fp8_e4m3" : r->f32 ? "float32" : r->bf16 ? "bfloat16" : "float16"; }
 int nvr_runner_set_kv_scales(nvr_model_runner_t *r, float k_scale, float v_scale) {
     if (!r->kv_fp8) return nvr::fail(NVR_ERR_UNSUPPORTED, "nvr_runner_set_kv_scales: the runner's KV cache is %s, not fp8", nvr_runner_kv_cache_dtype(r));
     if (!(k_scale > 0.f) || !(v_scale > 0.f) || std::isinf(k_scale) || std::isinf(v_scale))
@@ -559,6 +559,11 @@ int nvr_weight_quantize_fp8(const nvr_half *W, int64_t N, int64_t K, uint8_t *Wq
 int nvr_linear_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, nvr_half *y, void *s) {
     NO_F32("nvr_linear_fp8");
     return KO(linear_fp8(x, ldx, Wq, scales, T, K, N, y, (hipStream_t)s));
+}
+int nvr_lm_head_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t N, float *logits, float *part_val,
+                    int32_t *part_idx, int32_t *nparts, void *s) {
+    NO_F32("nvr_lm_head_fp8");
+    return KO(lm_head_fp8(x, ldx, Wq, scales, T, K, N, logits, part_val, part_idx, nparts, (hipStream_t)s));
 }
 int nvr_linear_silu_mul_fp8(const nvr_half *x, int64_t ldx, const uint8_t *Wq, const float *scales, int64_t T, int64_t K, int64_t I, nvr_half *out,
                             void *s) {
