@@ -134,7 +134,8 @@ typedef struct nvr_config {
                                           projections, a step behind a cached prefix or of a later chunk reads EVERY key, its own rows included, from the
                                           bytes (nvr_attn_prefill_paged_fp8) — so a prompt served behind a cached prefix or in chunks sees quantised K/V
                                           where the same prompt served whole sees its projections; decode always sees the bytes.  It needs a 16-bit dtype,
-                                          head_dim 64 / 128 and 1, 2 or 4 query heads per kv head, and for recompute_cached_prefix = 0 or
+                                          head_dim 64 / 128 and 1, 2 or 4 query heads per kv head (8 with a kvcache_block_size that is a power of two >= 64:
+                                          decode only — no shared-prefix or work-balanced launch, recompute_cached_prefix = 1, no chunked prefill), and for recompute_cached_prefix = 0 or
                                           enable_chunked_prefill = 1 a kvcache_block_size that is a power of two >= 64 (NVR_ERR_UNSUPPORTED otherwise); with
                                           such a block size it takes the shared-prefix decode launch (nvr_paged_attn_decode_shared_fp8); with a block size
                                           that is a power of two >= 16 (head_dim 128) / 32 (head_dim 64) its ragged decode batches take the work-balanced
@@ -640,8 +641,9 @@ NVR_API int nvr_paged_attn_decode_shared(const nvr_half *q, int64_t ldq, const n
 NVR_API int nvr_kv_store_fp8(const nvr_half *qkv, const int32_t *slot_mapping, int64_t T, int64_t H, int64_t KVH, int64_t D,
                              float k_scale, float v_scale, uint8_t *k_cache, uint8_t *v_cache, void *stream);
 /* K9 over such caches (attention.rs:225-235,264-318, A-8: the semantics of nvr_paged_attn_decode with K = k_scale * bytes, V = v_scale * bytes;
- * k_scale is folded into the softmax scale, v_scale multiplies the finished row).  D in {64, 128}, H / KVH in {1, 2, 4}, block_size at least one
- * row group of the kernel (8 rows at D = 128, 16 at D = 64); other shapes and "float32": NVR_ERR_UNSUPPORTED.  workspace:
+ * k_scale is folded into the softmax scale, v_scale multiplies the finished row).  D in {64, 128}, H / KVH in {1, 2, 4}; 8 with a block size that is a
+ * power of two >= 64 (the G heads of a query are the columns of 16-bit MFMAs, probabilities rounded to 16 bits in front of P.V; always the per-pair
+ * launches).  block_size at least one row group of the kernel (8 rows at D = 128, 16 at D = 64); other shapes and "float32": NVR_ERR_UNSUPPORTED.  workspace:
  * nvr_paged_attn_workspace_bytes.  tickets: [B * KVH] device words, ZERO before the first call and owned by these calls afterwards (the kernel
  * re-arms them; one call at a time per array), or NULL.  With tickets, a block_size that is a power of two >= 16 (D = 128) / 32 (D = 64) and a
  * pair count that fills rounds of one workgroup per (sequence, kv head) badly (more pairs than CUs, >= 15 % of the rounds' slots empty, contexts

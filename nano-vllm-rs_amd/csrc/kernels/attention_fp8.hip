@@ -15,7 +15,8 @@
 // row's dot product runs over D/16 lanes and the 64/(D/16) row-group slots of a wave are merged once, at the end.
 //
 // Two launches: one or more workgroups per (query, kv head) pair (attn_fp8_kernel, + attn_fp8_merge_kernel for split contexts), or — pair counts that fill the
-// per-pair rounds badly, ragged batches — workgroups that walk equal shares of all pairs' keys (attn_share_fp8_kernel).
+// per-pair rounds badly, ragged batches — workgroups that walk equal shares of all pairs' keys (attn_share_fp8_kernel).  G = 8 does not run here: its
+// per-pair launches go to the matrix cores (attn_fp8_mfma_kernel, attention_fp8_mfma.hip) with this file's partials and merge kernel.
 #include <algorithm>
 #include <type_traits>
 #include "kernels.h"
@@ -718,6 +719,30 @@ static int launch_attn_fp8(const AttnFp8Args &a, hipStream_t s) {
     return 0;
 }
 
+// G = 8 (attn_fp8_mfma_ok): attn_fp8_mfma_kernel (attention_fp8_mfma.hip) on the per-pair plan above — one workgroup per (query, kv head) from 192 pairs on,
+// else the context cut to reach ~256 workgroups — except that a partition keeps at least one 64-key step for each of the kernel's 4 waves; partitions
+// are whole 64-key steps, at most one per 64 keys of max_ctx (the workspace's cap); split contexts take the merge launch.
+template <int D>
+static int launch_attn_fp8_mfma(const AttnFp8Args &a, hipStream_t s) {
+    const int64_t mc = a.max_ctx > 0 ? a.max_ctx : 1, pairs = (int64_t)a.nq * a.KVH, units = (mc + 63) / 64;
+    int64_t want = 1;
+    if (a.workspace) want = pairs >= 192 ? 1 : (256 + pairs - 1) / pairs;
+    want = std::max<int64_t>(1, std::min<int64_t>(want, units / 4));
+    if (a.workspace_bytes) want = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)(a.workspace_bytes / ((size_t)a.nq * a.H * (D + 2) * sizeof(float)))));
+    const int64_t ps = ((mc + want - 1) / want + 63) / 64 * 64;
+    const int np = (int)((mc + ps - 1) / ps);
+    float *part_o = (float *)a.workspace, *part_ml = part_o + (int64_t)a.nq * a.H * np * D;
+    if (int rc = attn_fp8_mfma(a, (int32_t)ps, np, part_o, part_ml, s)) return rc;
+    if (np > 1) {
+        const int64_t rows = (int64_t)a.H * a.nq;
+        attn_fp8_merge_kernel<D><<<dim3((unsigned)((rows + 256 / (D / 4) - 1) / (256 / (D / 4)))), dim3(256), 0, s>>>(part_o, part_ml, a.ctx_lens, a.H, (int)ps, np, 0, 0,
+                                                                                                                   nullptr, rows, (half_t *)a.out);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "attention_fp8 (merge) launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
 int attention_fp8(const AttnFp8Args &a, hipStream_t s) {
     if (a.nq == 0) return 0;
     if (a.KVH <= 0 || a.H % a.KVH) return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: H=%d not a multiple of KVH=%d", a.H, a.KVH);
@@ -734,9 +759,11 @@ int attention_fp8(const AttnFp8Args &a, hipStream_t s) {
             return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: the shared-prefix pass takes D in {64,128}, H/KVH in {1,2,4}, block_size a power of two >= 64 "
                              "(D=%d H=%d KVH=%d block_size=%d)", a.D, a.H, a.KVH, a.block_size);
     }
+    if (G == 8 && attn_fp8_mfma_ok(a.D, a.H, a.KVH, a.block_size))      // wide groups: the MFMA kernel (tickets / balance_hint: no work-balanced instance, per-pair launches)
+        return a.D == 128 ? launch_attn_fp8_mfma<128>(a, s) : launch_attn_fp8_mfma<64>(a, s);
     if (!shape_ok || a.block_size < 64 / (a.D / 16))                    // a block holds at least one row group (8 rows at D = 128, 16 at D = 64)
-        return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: unsupported head_dim=%d / group=%d / block_size=%d (D in {64,128}, G in {1,2,4}, block_size >= %d)",
-                         a.D, G, a.block_size, shape_ok ? 64 / (a.D / 16) : 8);
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: unsupported head_dim=%d / group=%d / block_size=%d (D in {64,128}, G in {1,2,4}, block_size >= %d; "
+                         "G = 8: block_size a power of two >= 64)", a.D, G, a.block_size, shape_ok ? 64 / (a.D / 16) : 8);
 #define NVR_ATTN8_CASE(DD, GG) if (a.D == DD && G == GG) return launch_attn_fp8<DD, GG>(a, s);
     NVR_ATTN8_CASE(128, 1) NVR_ATTN8_CASE(128, 2) NVR_ATTN8_CASE(128, 4) NVR_ATTN8_CASE(64, 1) NVR_ATTN8_CASE(64, 2) NVR_ATTN8_CASE(64, 4)
 #undef NVR_ATTN8_CASE

@@ -50,6 +50,15 @@ __device__ __forceinline__ void glds_pieces(const T *const (&src)[N], unsigned l
     }
 }
 
+// Byte images of K / V rows (flash_prefill_fp8.hip's header comment derives them; attention_fp8_mfma.hip stages V the same way): chunk XOR of
+// the V image, and ds_read_b64_tr_b8, the hardware-transposed LDS read of 8 rows x 16 columns of bytes
+typedef int int2_t __attribute__((ext_vector_type(2)));
+template <int D>
+__device__ __forceinline__ int v8_swz(int key) { return D == 128 ? ((key >> 1) & 7) : ((key >> 2) & 3); }
+__device__ __forceinline__ int2_t lds_read_tr8(const char *lds_addr) {
+    return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) int2_t *)lds_addr);
+}
+
 // max over the four 16-lane rows of a wave (the 4 key quads of a query), in the vector ALU: v_permlane16_swap / v_permlane32_swap of a
 // value with itself leave {own, partner} in the two results (an LDS round trip per ds_bpermute before: two dependent ones per step)
 __device__ __forceinline__ float max_over_rows(float v) {

@@ -52,8 +52,6 @@
 
 namespace nvr { namespace NVR_DT_NS {
 
-typedef int int2_t __attribute__((ext_vector_type(2)));
-
 struct FlashFp8Params {
     const half_t *q; int64_t ldq;
     const uint8_t *k, *v;
@@ -65,11 +63,9 @@ struct FlashFp8Params {
     half_t *out;
 };
 
-// chunk XORs of the byte images (header comment)
+// chunk XORs of the byte images (header comment; v8_swz and lds_read_tr8: flash_common.h)
 template <int D>
 __device__ __forceinline__ int k8_swz(int key) { return D == 128 ? (((key >> 1) & 1) | (((key >> 3) & 3) << 1)) : ((key >> 3) & 3); }
-template <int D>
-__device__ __forceinline__ int v8_swz(int key) { return D == 128 ? ((key >> 1) & 7) : ((key >> 2) & 3); }
 
 // 8 e4m3 bytes (two dwords, byte order = element order) -> 8 values of the build's 16-bit type, exactly
 __device__ __forceinline__ half8_t fp8x8_to_half8(int2_t w) {
@@ -81,10 +77,6 @@ __device__ __forceinline__ half8_t fp8x8_to_half8(int2_t w) {
     const half2_t a = NVR_CVT8(w[0], false), b = NVR_CVT8(w[0], true), c = NVR_CVT8(w[1], false), d = NVR_CVT8(w[1], true);
 #undef NVR_CVT8
     return __builtin_shufflevector(__builtin_shufflevector(a, b, 0, 1, 2, 3), __builtin_shufflevector(c, d, 0, 1, 2, 3), 0, 1, 2, 3, 4, 5, 6, 7);
-}
-// ds_read_b64_tr_b8: the hardware-transposed LDS read of 8 rows x 16 columns of bytes (lane layout: header comment)
-__device__ __forceinline__ int2_t lds_read_tr8(const char *lds_addr) {
-    return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) int2_t *)lds_addr);
 }
 
 template <int D, int G>

@@ -145,12 +145,16 @@ size_t attn_workspace_bytes(int64_t nq, int64_t H, int64_t D, int64_t max_ctx);
 int attention(const AttnArgs &a, bool paged, hipStream_t s);
 
 // FP8 (e4m3) KV cache: rows of the roped K and V columns of qkv [T, (H+2KVH)D] -> byte caches at slots (< 0 skips), byte = e4m3(x / scale), round to
-// nearest even, clamped to +-448; paged decode attention over such caches (D in {64,128}, H/KVH in {1,2,4}; workspace as for attention)
+// nearest even, clamped to +-448; paged decode attention over such caches (D in {64,128}, H/KVH in {1,2,4}, or 8 where attn_fp8_mfma_ok; workspace as for attention)
 int kv_store_fp8(const half_bits *qkv, const int32_t *slots, int64_t T, int64_t H, int64_t KVH, int64_t D, float k_scale, float v_scale,
                  uint8_t *k_cache, uint8_t *v_cache, hipStream_t s);
 int attention_fp8(const AttnFp8Args &a, hipStream_t s);
 // the work-balanced form of attention_fp8 can run: block_size a power of two >= the kernel's chunk (16 keys at D = 128, 32 at D = 64)
 bool attn_share_fp8_ok(int D, int block_size);
+// H/KVH = 8 on the matrix cores (attention_fp8_mfma.hip): D in {64,128}, block_size a power of two >= 64.  attn_fp8_mfma: the kernel's launch alone, on a given
+// plan (num_parts == 1: 16-bit rows; else partitions of part_size keys, a multiple of 64, as f32 partials for attention_fp8's merge); callers use attention_fp8
+bool attn_fp8_mfma_ok(int D, int H, int KVH, int block_size);
+int attn_fp8_mfma(const AttnFp8Args &a, int32_t part_size, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s);
 
 bool flash_prefill_ok(int D, int H, int KVH);
 int flash_tile_positions(int H, int KVH);

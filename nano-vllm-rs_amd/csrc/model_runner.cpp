@@ -86,9 +86,12 @@ int nvr_model_runner::init() {                                       // ModelRun
     Vl = V / tp; vocab_start = rank * Vl; if (rank == tp - 1) Vl = V - vocab_start;   // embed_head.rs:57-59
     scale = 1.0f / std::sqrt((float)D);                                           // attention.rs:45
     block_size = cfg.kvcache_block_size;
-    if (kv_fp8 && ((D != 64 && D != 128) || KVH <= 0 || H % KVH || (H / KVH != 1 && H / KVH != 2 && H / KVH != 4) || block_size < 64 / (D / 16)))
-        return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8: head_dim %ld, %ld query heads per kv head, block size %ld (head_dim 64 or 128; 1, 2 or 4; "
-                         "at least 8 rows at head_dim 128, 16 at 64)", (long)D, (long)(KVH > 0 ? H / KVH : 0), (long)block_size);
+    // 8 query heads per kv head decode on the matrix cores (kernels/attention_fp8_mfma.hip), which takes its 64-key steps from inside one block
+    if (kv_fp8 && !KD(attn_fp8_mfma_ok((int)D, (int)H, (int)KVH, (int)block_size)) &&
+        ((D != 64 && D != 128) || KVH <= 0 || H % KVH || (H / KVH != 1 && H / KVH != 2 && H / KVH != 4) || block_size < 64 / (D / 16)))
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8: head_dim %ld, %ld query heads per kv head, block size %ld (head_dim 64 or 128; 1, 2 or 4 "
+                         "with at least 8 rows at head_dim 128, 16 at 64; 8 with a block size that is a power of two >= 64)", (long)D,
+                         (long)(KVH > 0 ? H / KVH : 0), (long)block_size);
     // a prefill step behind a cached prefix or of a later chunk reads the byte cache through the block tables (kernels/flash_prefill_fp8.hip)
     if (kv_fp8 && (!cfg.recompute_cached_prefix || cfg.enable_chunked_prefill) && !KD(flash_prefill_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size)))
         return nvr::fail(NVR_ERR_UNSUPPORTED, "kv_cache_dtype fp8 with recompute_cached_prefix = 0 or enable_chunked_prefill = 1 (got %d / %d) needs a "
@@ -178,7 +181,8 @@ int nvr_model_runner::init() {                                       // ModelRun
         NVR_HIP_CHECK(hipMemset(attn_tickets, 0, (size_t)(max_seqs * KVH) * sizeof(unsigned int)));
     }
     // an fp8 runner's decode steps may take the work-balanced attention launch: the counters exist, the block size suits the kernel, NVR_ATTN_SHARE is not 0
-    share_fp8 = kv_fp8 && attn_tickets && env.attn_share != 0 && KD(attn_share_fp8_ok((int)D, (int)block_size));
+    // (8 query heads per kv head: the MFMA kernel has no work-balanced instance, its steps are per-pair launches)
+    share_fp8 = kv_fp8 && attn_tickets && env.attn_share != 0 && KD(attn_share_fp8_ok((int)D, (int)block_size)) && H / KVH != 8;
     // step-input arena
     auto carve = [&](size_t &off, size_t bytes) { off = in_bytes; in_bytes += (bytes + 255) / 256 * 256; };
     // prefill region (the start of the arena): capacity for the largest step; a step lays its arrays out back to back for its own
