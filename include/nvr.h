@@ -135,7 +135,8 @@ typedef struct nvr_config {
                                           bytes (nvr_attn_prefill_paged_fp8) — so a prompt served behind a cached prefix or in chunks sees quantised K/V
                                           where the same prompt served whole sees its projections; decode always sees the bytes.  It needs a 16-bit dtype,
                                           head_dim 64 / 128 and 1, 2 or 4 query heads per kv head (8 with a kvcache_block_size that is a power of two >= 64:
-                                          decode only — no shared-prefix or work-balanced launch, recompute_cached_prefix = 1, no chunked prefill), and for recompute_cached_prefix = 0 or
+                                          decode only — no shared-prefix launch, recompute_cached_prefix = 1, no chunked prefill; its ragged decode batches of up to two
+                                          (sequence, kv head) pairs per CU and >= 8 (head_dim 128) / 14 (head_dim 64) x 64 keys per CU take the work-balanced launch), and for recompute_cached_prefix = 0 or
                                           enable_chunked_prefill = 1 a kvcache_block_size that is a power of two >= 64 (NVR_ERR_UNSUPPORTED otherwise); with
                                           such a block size it takes the shared-prefix decode launch (nvr_paged_attn_decode_shared_fp8); with a block size
                                           that is a power of two >= 16 (head_dim 128) / 32 (head_dim 64) its ragged decode batches take the work-balanced
@@ -354,7 +355,7 @@ NVR_API int64_t nvr_runner_last_shared_prefix_len(const nvr_model_runner_t *r);
  * K / V once, into the caches), 2 = the caches through the block tables (cached prefixes, prompt chunks); -1 = the last step was a decode */
 NVR_API int nvr_runner_last_prefill_kv_source(const nvr_model_runner_t *r);
 NVR_API int64_t nvr_runner_last_shared_prefix_rows(const nvr_model_runner_t *r);   /* sequences of that step inside the sharing group */
-/* 1 when the last decode step's contexts were RAGGED enough (their sum < batch x longest / 1.3, up to 1024 (sequence, kv head) pairs, >= 6 x 64 keys per CU) for the
+/* 1 when the last decode step's contexts were RAGGED enough (their sum < batch x longest / 1.3, up to 1024 (sequence, kv head) pairs, >= 6 x 64 keys per CU; fp8 KV cache with 8 query heads per kv head: up to two pairs per CU, >= 8 / 14 x 64 keys per CU at head_dim 128 / 64) for the
  * work-balanced attention launch — two or three workgroups per CU walking equal shares of all pairs' keys instead of workgroups per pair sized by the longest
  * context (Attention::flash_attention_decode, attention.rs:225-235: same result within one f32 merge); 0 otherwise, and for prefill steps. */
 NVR_API int32_t nvr_runner_last_decode_ragged(const nvr_model_runner_t *r);
@@ -642,8 +643,9 @@ NVR_API int nvr_kv_store_fp8(const nvr_half *qkv, const int32_t *slot_mapping, i
                              float k_scale, float v_scale, uint8_t *k_cache, uint8_t *v_cache, void *stream);
 /* K9 over such caches (attention.rs:225-235,264-318, A-8: the semantics of nvr_paged_attn_decode with K = k_scale * bytes, V = v_scale * bytes;
  * k_scale is folded into the softmax scale, v_scale multiplies the finished row).  D in {64, 128}, H / KVH in {1, 2, 4}; 8 with a block size that is a
- * power of two >= 64 (the G heads of a query are the columns of 16-bit MFMAs, probabilities rounded to 16 bits in front of P.V; always the per-pair
- * launches).  block_size at least one row group of the kernel (8 rows at D = 128, 16 at D = 64); other shapes and "float32": NVR_ERR_UNSUPPORTED.  workspace:
+ * power of two >= 64 (the G heads of a query are the columns of 16-bit MFMAs, probabilities rounded to 16 bits in front of P.V; its
+ * work-balanced launch — with tickets, under the same pair-count rule — gives every WAVE of one or two workgroups per CU an equal share of all pairs' 64-key steps;
+ * measured slower than the per-pair launches on uniform contexts, DESIGN 6c: pass tickets at 8 heads per kv head for ragged batches).  block_size at least one row group of the kernel (8 rows at D = 128, 16 at D = 64); other shapes and "float32": NVR_ERR_UNSUPPORTED.  workspace:
  * nvr_paged_attn_workspace_bytes.  tickets: [B * KVH] device words, ZERO before the first call and owned by these calls afterwards (the kernel
  * re-arms them; one call at a time per array), or NULL.  With tickets, a block_size that is a power of two >= 16 (D = 128) / 32 (D = 64) and a
  * pair count that fills rounds of one workgroup per (sequence, kv head) badly (more pairs than CUs, >= 15 % of the rounds' slots empty, contexts

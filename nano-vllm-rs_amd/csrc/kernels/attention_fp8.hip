@@ -16,7 +16,8 @@
 //
 // Two launches: one or more workgroups per (query, kv head) pair (attn_fp8_kernel, + attn_fp8_merge_kernel for split contexts), or — pair counts that fill the
 // per-pair rounds badly, ragged batches — workgroups that walk equal shares of all pairs' keys (attn_share_fp8_kernel).  G = 8 does not run here: its
-// per-pair launches go to the matrix cores (attn_fp8_mfma_kernel, attention_fp8_mfma.hip) with this file's partials and merge kernel.
+// launches go to the matrix cores (attn_fp8_mfma_kernel per pair, attn_share_fp8_mfma_kernel work-balanced: attention_fp8_mfma.hip) with this file's partials,
+// merge kernel and launch rule.
 #include <algorithm>
 #include <type_traits>
 #include "kernels.h"
@@ -725,6 +726,16 @@ static int launch_attn_fp8(const AttnFp8Args &a, hipStream_t s) {
 template <int D>
 static int launch_attn_fp8_mfma(const AttnFp8Args &a, hipStream_t s) {
     const int64_t mc = a.max_ctx > 0 ? a.max_ctx : 1, pairs = (int64_t)a.nq * a.KVH, units = (mc + 63) / 64;
+    // Work-balanced form (attn_share_fp8_mfma_kernel) under launch_attn_fp8's rule: tickets and a workspace with one slot per 64 keys of max_ctx (a pair meets at
+    // most that many workers), then the pair-count case, a caller's balance_hint (workgroups; the kernel derives its worker count from the units), or
+    // NVR_ATTN_SHARE=2 (two workgroups per CU: both are resident).  NVR_ATTN_SHARE=0 or no tickets: the per-pair launches below, as before.
+    if (a.shared_len <= 0 && a.workspace && a.tickets && a.nq <= 1024 && share_enabled()) {
+        const int64_t cus = share_workgroups(), rounds = (pairs + cus - 1) / cus;
+        const int64_t cap = a.workspace_bytes ? (int64_t)(a.workspace_bytes / ((size_t)a.nq * a.H * (D + 2) * sizeof(float))) : units;
+        const bool by_count = pairs > cus && rounds * cus * 100 >= pairs * 115 && mc >= 256;
+        const int64_t nw = a.balance_hint > 0 ? a.balance_hint : share_mode() == 2 ? 2 * cus : cus;
+        if ((by_count || a.balance_hint > 0 || share_mode() == 2) && pairs < 2048 && cap >= units) return attn_share_fp8_mfma(a, (int32_t)units, (int32_t)nw, s);
+    }
     int64_t want = 1;
     if (a.workspace) want = pairs >= 192 ? 1 : (256 + pairs - 1) / pairs;
     want = std::max<int64_t>(1, std::min<int64_t>(want, units / 4));
@@ -759,7 +770,7 @@ int attention_fp8(const AttnFp8Args &a, hipStream_t s) {
             return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: the shared-prefix pass takes D in {64,128}, H/KVH in {1,2,4}, block_size a power of two >= 64 "
                              "(D=%d H=%d KVH=%d block_size=%d)", a.D, a.H, a.KVH, a.block_size);
     }
-    if (G == 8 && attn_fp8_mfma_ok(a.D, a.H, a.KVH, a.block_size))      // wide groups: the MFMA kernel (tickets / balance_hint: no work-balanced instance, per-pair launches)
+    if (G == 8 && attn_fp8_mfma_ok(a.D, a.H, a.KVH, a.block_size))      // wide groups: the MFMA kernels (per-pair launches, or with tickets and under the rule the work-balanced one)
         return a.D == 128 ? launch_attn_fp8_mfma<128>(a, s) : launch_attn_fp8_mfma<64>(a, s);
     if (!shape_ok || a.block_size < 64 / (a.D / 16))                    // a block holds at least one row group (8 rows at D = 128, 16 at D = 64)
         return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: unsupported head_dim=%d / group=%d / block_size=%d (D in {64,128}, G in {1,2,4}, block_size >= %d; "

@@ -36,11 +36,13 @@
 #include "kernels.h"
 #include "device_utils.h"
 #include "flash_common.h"
+#include "attn_merge.h"
 #include "../common.h"
 
 namespace nvr { namespace NVR_DT_NS {
 
 typedef unsigned int uint4_t __attribute__((ext_vector_type(4)));
+typedef unsigned int uint2_t __attribute__((ext_vector_type(2)));
 
 struct AttnFp8MfmaParams {
     const half_t *q; int64_t ldq;
@@ -273,6 +275,269 @@ __global__ __launch_bounds__(256, 2) void attn_fp8_mfma_kernel(AttnFp8MfmaParams
     }
 }
 
+// ---- work-balanced form ------------------------------------------------------------------------------------------------------------
+// The data path above on another work split: ONE SHARE PER WAVE.  The four waves of attn_fp8_mfma_kernel never meet inside the key stream (own V ring, own K
+// registers, own vmcnt waits), so here they do not meet at all.  Unit = one 64-key step; query t owns ceil(ctx_lens[t] / 64) units per kv head and the units of all
+// (query, kv head) pairs, query-major, form one line of U_tot units (attn_share_fp8_kernel's prefix table pre[] / cx[] in LDS, built by wave 0: the barrier behind
+// it is the only one of the kernel).  The launch is nw workgroups = W = 4·nw workers; W_eff = clamp(U_tot / 4, 1, W) of them (numbered wave·nw + workgroup) — derived here, from ctx_lens and
+// nw alone, so an eager step and a replayed graph cut alike — walk units [w·U_tot / W_eff, (w + 1)·U_tot / W_eff): no share is empty, so the number of workers a
+// pair meets (np = last - first + 1) is exact, and no share is shorter than four steps unless the whole line is.  A share is a suffix of one pair, whole pairs, a
+// prefix of another: a SEGMENT each, streamed by the per-pair kernel's wave loop with stride 1.  A pair inside one share (np == 1) is normalised and written from
+// the accumulators; a cut pair leaves one f32 partial per worker (the per-pair launch's units; slot = worker - first worker of the pair), the worker drains its
+// stores and takes the pair's ticket (release / acquire as in attn_share_fp8_kernel; one lane takes it, the wave reads it by v_readfirstlane), and the last arriver
+// merges the np partials in slot order (merge_partitions), writes the rows and re-arms the counter: two launches agree bit for bit.
+// Segment boundary: stores count in vmcnt on gfx950, so the tail's row / partial stores would stand in the same queue as the next segment's hand-counted requests.
+// The boundary DRAINS (vmcnt(0) behind the tail; the next segment's Q and block-table chunk land by load_bt_chunk's own wait) — the next segment is not opened
+// under the tail.  Workers >= W_eff only take part in the zero rows (queries without keys, dealt over the workgroups).
+template <int D, int G>
+__global__ __launch_bounds__(256, 2) void attn_share_fp8_mfma_kernel(AttnFp8MfmaParams p, unsigned int *tickets, int nq) {
+    static_assert(G >= 1 && G <= 16 && (D == 64 || D == 128), "the G heads of a kv head are the 16 columns of one MFMA");
+    constexpr int KT = 64, WAVES = 4;
+    constexpr int CPR = D / 16, NJ = D / 64, NMT = KT / 16, NK2 = KT / 32, NDT = D / 16;
+    constexpr int OPB = KT * D, NP = OPB / 1024, WRING = 2 * OPB;
+    __shared__ __attribute__((aligned(16))) char smem[WAVES * WRING];
+    __shared__ int pre[1025];                               // pre[t] = units of the queries in front of t (a query's KVH pairs have the same count)
+    __shared__ int cx[1024];                                // ctx_lens[t]
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int r = lane & 15, g4 = lane >> 4;
+    const int nw = gridDim.x;
+    if (wave == 0) {
+        int base = 0;
+        for (int k = 0; k < nq; k += 64) {
+            const int tq = k + lane;
+            const int c = tq < nq ? p.ctx_lens[tq] : 0;
+            int un = (c + KT - 1) / KT;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(un, o, 64); if (lane >= o) un += v; }
+            if (tq < nq) { pre[tq + 1] = base + un; cx[tq] = c; }
+            base += __shfl(un, 63, 64);
+        }
+        if (lane == 0) pre[0] = 0;
+    }
+    __syncthreads();
+    // a query without keys owns no unit: its output row is zero, as in attn_fp8_mfma_kernel
+    for (int t0 = blockIdx.x; t0 < nq; t0 += nw)
+        if (cx[t0] == 0)
+            for (int x = threadIdx.x; x < p.H * D; x += WAVES * 64) p.out[(int64_t)t0 * p.H * D + x] = (half_t)0.f;
+    const int utot = p.KVH * __builtin_amdgcn_readfirstlane(pre[nq]);            // (< 2^31: the launch checks pairs x slots)
+    const int W_eff = max(1, min(utot / 4, WAVES * nw));
+    const int worker = wave * nw + (int)blockIdx.x;         // interleaved over the workgroups: W_eff < W leaves waves idle in EVERY workgroup, not whole CUs
+    if (worker >= W_eff) return;
+    const int ub = (int)((long long)worker * utot / W_eff), ue = (int)((long long)(worker + 1) * utot / W_eff);
+    if (ub >= ue) return;                                   // (no unit at all: every query is a zero row)
+    const int row_bytes = p.KVH * D;
+
+    // ---- state of the segment being streamed: wave-uniform (SGPRs) ----
+    int t = 0, g = 0, np = 1, slot = 0, p0 = 0, pend = 0, nsteps = 0;
+    int bt_reg = 0, bt_chunk = -1;
+    auto load_bt_chunk = [&](int c) {                        // 64 block-table entries of query t (lane j: entry 64·c + j) by a load that waits for itself — and for
+        bt_chunk = c;                                        // everything older: the segment's Q fragments, the stores of the segment in front
+        const int idx = min((c << 6) + lane, p.max_blocks - 1);
+        const int32_t *src = p.block_tables + (int64_t)t * p.max_blocks + idx;
+        asm volatile("global_load_dword %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=v"(bt_reg) : "v"(src) : "memory");
+    };
+    half8_t qf[NJ][2];                                       // Qᵀ fragments of the segment's pair in the permutation of the K requests
+
+    // lane constants of a step's requests and of the V reads (attn_fp8_mfma_kernel)
+    const int krow = (r >> 2) * 8 + (r & 3);
+    const int vrow0 = lane / CPR, vchunk = lane % CPR;
+    const unsigned lds_wave = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem + (unsigned)wave * WRING;
+    struct StepAt { int64_t sbase; int lim; };
+    auto step_at = [&](int kt) -> StepAt {                  // kt < pend <= ctx: an entry of the context
+        const int bi = kt >> p.bs_shift;
+        if ((bi >> 6) != bt_chunk) load_bt_chunk(bi >> 6);
+        const int64_t row0 = (int64_t)__builtin_amdgcn_readlane(bt_reg, bi & 63) * p.block_size + (kt & (p.block_size - 1));
+        return {(row0 * p.KVH + g) * D, pend - 1 - kt};
+    };
+    auto load_k = [&](uint4_t (&kr)[NMT][NJ], const StepAt &at) {              // plain loads: the compiler waits for them where they are used
+        const uint8_t *kbase = p.k + at.sbase;
+#pragma unroll
+        for (int mt = 0; mt < NMT; ++mt) {
+            const unsigned ko = (unsigned)(min(krow + (mt >> 1) * 32 + (mt & 1) * 4, at.lim) * row_bytes + g4 * 16);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) kr[mt][j] = __builtin_nontemporal_load(reinterpret_cast<const uint4_t *>(kbase + ko + j * 64));
+        }
+    };
+    auto stage_v = [&](int vslot, const StepAt &at) {                            // LDS-DMA, invisible to the compiler's wait counting
+        const uint8_t *vsrc[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int row = i * (64 / CPR) + vrow0;
+            vsrc[i] = p.v + at.sbase + (unsigned)(min(row, at.lim) * row_bytes + ((vchunk ^ v8_swz<D>(row)) << 4));
+        }
+        glds_pieces<NP, 1024>(vsrc, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_wave + vslot * OPB)));
+    };
+    auto v_landed = [&](bool more) {
+        if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+
+    float4_t o[NDT], ol;
+    float m;
+    const float c2 = p.scale * 1.44269504088896340736f;
+    half8_t ones;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ones[e] = (half_t)1.0f;
+    const int vrow = g4 * 8 + (r >> 1);
+    const int vxor = v8_swz<D>(vrow);
+    const int voff = vrow * D + ((r & 1) << 3);
+
+    // the step at kt (attn_fp8_mfma_kernel's arithmetic): K in kr, V image in ring slot vslot; `more`: the K rows of the step at `next` are requested
+    auto compute = [&](int vslot, const uint4_t (&kr)[NMT][NJ], int kt, bool more, const StepAt &next) {
+        const char *vl = smem + wave * WRING + vslot * OPB;
+        float4_t s[NMT];
+#pragma unroll
+        for (int mt = 0; mt < NMT; ++mt) {
+            s[mt] = (float4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) s[mt] = mfma16(fp8x8_to_half8(kr[mt][j][2 * h], kr[mt][j][2 * h + 1]), qf[j][h], s[mt]);
+        }
+#pragma unroll
+        for (int mt = 0; mt < NMT; ++mt) asm volatile("" : "+v"(s[mt]));
+        v_landed(more);
+        if (more) stage_v(vslot ^ 1, next);
+        if (kt + KT > pend) {                                      // only a segment's last step, where it ends the context
+#pragma unroll
+            for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (kt + (mt >> 1) * 32 + g4 * 8 + (mt & 1) * 4 + e >= pend) s[mt][e] = -INFINITY;
+        }
+        float mx = fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3]));
+#pragma unroll
+        for (int mt = 1; mt < NMT; ++mt) mx = fmaxf(fmaxf(mx, s[mt][0]), fmaxf(fmaxf(s[mt][1], s[mt][2]), s[mt][3]));
+        mx = max_over_rows(mx);
+        const float mn = fmaxf(m, mx);                             // finite: key kt < pend is visible to every column
+        const float alpha = __builtin_amdgcn_exp2f((m - mn) * c2);
+        const bool moved = mn != m;
+        m = mn;
+        const float mc = -mn * c2;
+        half8_t pf[NK2];
+#pragma unroll
+        for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pf[mt >> 1][(mt & 1) * 4 + e] = (half_t)__builtin_amdgcn_exp2f(fmaf(s[mt][e], c2, mc));
+        if (__any(moved)) {
+            ol *= alpha;
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < NK2; ++k2) {
+            ol = mfma16(ones, pf[k2], ol);
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                const int2_t vb = lds_read_tr8(vl + k2 * 32 * D + voff + ((dt ^ vxor) << 4));
+                o[dt] = mfma16(fp8x8_to_half8((unsigned)vb[0], (unsigned)vb[1]), pf[k2], o[dt]);
+            }
+        }
+    };
+
+    uint4_t ka[NMT][NJ], kb[NMT][NJ];
+#pragma unroll
+    for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { ka[mt][j] = (uint4_t){0u, 0u, 0u, 0u}; kb[mt][j] = (uint4_t){0u, 0u, 0u, 0u}; }
+
+    for (int u = ub; u < ue;) {
+        // ---- open the segment that starts at unit u ----
+        {
+            int lo = 0, hi = nq;                            // the query of unit u: the last t with KVH * pre[t] <= u (queries without keys own no unit)
+            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (p.KVH * __builtin_amdgcn_readfirstlane(pre[mid]) <= u) lo = mid; else hi = mid; }
+            t = lo;
+            const int pt = __builtin_amdgcn_readfirstlane(pre[t]), ut = __builtin_amdgcn_readfirstlane(pre[t + 1]) - pt;
+            const int rem = u - p.KVH * pt;
+            g = rem / ut;
+            const int lu = rem - g * ut, seg = min(ut - lu, ue - u);
+            // workers that touch this pair: unit x belongs to worker floor(((x + 1) * W_eff - 1) / utot)
+            const int S = p.KVH * pt + g * ut;          // the pair's first unit; its last: S + ut - 1
+            const int wf = (int)(((long long)(S + 1) * W_eff - 1) / utot), wl = (int)(((long long)(S + ut) * W_eff - 1) / utot);
+            np = wl - wf + 1; slot = worker - wf;
+            p0 = lu * KT; pend = min(__builtin_amdgcn_readfirstlane(cx[t]), (lu + seg) * KT); nsteps = seg;
+            u += seg;
+        }
+        {
+            const half_t *qptr = p.q + (int64_t)t * p.ldq + (int64_t)(g * G + min(r, G - 1)) * D + g4 * 16;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) qf[j][h] = *reinterpret_cast<const half8_t *>(qptr + j * 64 + h * 8);
+        }
+        load_bt_chunk((p0 >> p.bs_shift) >> 6);
+        // everything the compiler knows to be in flight lands HERE, in front of the first hand-counted request
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) asm volatile("" :: "v"(qf[j][h]));
+        m = -INFINITY; ol = (float4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NDT; ++i) o[i] = (float4_t){0.f, 0.f, 0.f, 0.f};
+
+        // ---- stream its steps: ring slot and register set are compile-time constants, no K load under a condition of its own ----
+        {
+            StepAt at = step_at(p0);
+            stage_v(0, at); load_k(ka, at);
+            for (int st = 0;;) {
+                if (st + 1 >= nsteps) { compute(0, ka, p0 + st * KT, false, at); break; }
+                at = step_at(p0 + (st + 1) * KT); load_k(kb, at);
+                compute(0, ka, p0 + st * KT, true, at);
+                st += 1;
+                if (st + 1 >= nsteps) { compute(1, kb, p0 + st * KT, false, at); break; }
+                at = step_at(p0 + (st + 1) * KT); load_k(ka, at);
+                compute(1, kb, p0 + st * KT, true, at);
+                st += 1;
+            }
+        }
+
+        // ---- its end: lane r < G holds head r (accumulator e of o[dt]: d = 16·dt + 4·g4 + e; every row of the ones-product holds the sum) ----
+        const int64_t row0 = (int64_t)t * p.H + (int64_t)g * G;
+        const float L = ol[0];
+        if (np == 1) {
+            if (r < G) {
+                half_t *orow = p.out + (row0 + r) * D + g4 * 4;
+#pragma unroll
+                for (int dt = 0; dt < NDT; ++dt) {
+                    const float4_t acc = o[dt] * p.v_scale;
+                    half4_t hv;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) hv[e] = (half_t)(L > 0.f ? acc[e] / L : 0.f);
+                    *reinterpret_cast<half4_t *>(orow + dt * 16) = hv;
+                }
+            }
+        } else {
+            const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(p.part_o + row0 * p.num_parts * D, 0, (int)(G * p.num_parts * D * 4), 0x00020000);
+            const auto rs_ml = __builtin_amdgcn_make_buffer_rsrc(p.part_ml + row0 * p.num_parts * 2, 0, (int)(G * p.num_parts * 2 * 4), 0x00020000);
+            if (r < G) {
+                const int sl = r * p.num_parts + slot;
+#pragma unroll
+                for (int dt = 0; dt < NDT; ++dt)
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, o[dt] * p.v_scale), rs_o, (sl * D + dt * 16 + g4 * 4) * 4, 0, 16);
+                if (g4 == 0) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2_t, (float2_t){m * p.scale, L}), rs_ml, sl * 8, 0, 16);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the wave's partial is out ...
+            unsigned int *cnt = tickets + (int64_t)t * p.KVH + g;
+            unsigned int tk = 0;
+            if (lane == 0) tk = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                  // ... one ticket
+            tk = (unsigned)__builtin_amdgcn_readfirstlane((int)tk);
+            if (tk == (unsigned)(np - 1)) {                                   // the last of the pair's workers to finish merges it
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");        // keeps the sc1 loads below the ticket
+                constexpr int TPH = D / 4;
+                for (int x = lane; x < G * TPH; x += 64) {
+                    const int i = x / TPH, d = (x % TPH) * 4;
+                    const half4_t hv = merge_partitions(np,
+                        [&](int pi) { return __builtin_bit_cast(float2_t, __builtin_amdgcn_raw_buffer_load_b64(rs_ml, (i * p.num_parts + pi) * 8, 0, 16)); },
+                        [&](int pi) { return __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rs_o, ((i * p.num_parts + pi) * D + d) * 4, 0, 16)); });
+                    *reinterpret_cast<half4_t *>(p.out + (row0 + i) * D + d) = hv;
+                }
+                if (lane == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm for the next launch
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the boundary drains: no store of this tail stands among the next segment's hand-counted requests
+    }
+}
+
 bool attn_fp8_mfma_ok(int D, int H, int KVH, int block_size) {
     if (KVH <= 0 || H % KVH) return false;
     return (D == 64 || D == 128) && H / KVH == 8 && block_size >= 64 && (block_size & (block_size - 1)) == 0;
@@ -294,6 +559,28 @@ int attn_fp8_mfma(const AttnFp8Args &a, int32_t part_size, int32_t num_parts, fl
     else attn_fp8_mfma_kernel<64, 8><<<grid, block, 0, s>>>(p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "attn_fp8_mfma launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// The work-balanced launch: nw workgroups (4·nw workers) over `slots` partial slots per (query, head) in the workspace — one per 64 keys of max_ctx, the most
+// workers a pair can meet.  The rule that selects it: launch_attn_fp8_mfma, attention_fp8.hip.
+int attn_share_fp8_mfma(const AttnFp8Args &a, int32_t slots, int32_t nw, hipStream_t s) {
+    if (!attn_fp8_mfma_ok(a.D, a.H, a.KVH, a.block_size) || !a.tickets || !a.workspace || a.nq > 1024 || slots < 1 || nw < 1 ||
+        (int64_t)slots * 64 < a.max_ctx || (int64_t)8 * slots * a.D * 4 > 0x7fffffff || (int64_t)a.nq * a.KVH * slots > 0x7fffffff)
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "attn_share_fp8_mfma: D=%d H=%d KVH=%d block_size=%d nq=%d, %d slots for max_ctx %d, %d workgroups (attn_fp8_mfma_ok, "
+                         "tickets and a workspace, nq <= 1024, one slot per 64 keys of max_ctx)", a.D, a.H, a.KVH, a.block_size, a.nq, slots, a.max_ctx, nw);
+    if (a.workspace_bytes && (size_t)a.nq * a.H * slots * (a.D + 2) * sizeof(float) > a.workspace_bytes)
+        return nvr::fail(NVR_ERR_INVALID_ARG, "attn_share_fp8_mfma: %d slots of %d queries x %d heads do not fit %zu workspace bytes", slots, a.nq, a.H, a.workspace_bytes);
+    AttnFp8MfmaParams p{};
+    p.q = (const half_t *)a.q; p.ldq = a.ldq; p.k = a.k; p.v = a.v; p.ctx_lens = a.ctx_lens; p.block_tables = a.block_tables;
+    p.max_blocks = a.max_blocks; p.block_size = a.block_size; p.bs_shift = __builtin_ctz(a.block_size);
+    p.H = a.H; p.KVH = a.KVH; p.scale = a.scale * a.k_scale; p.v_scale = a.v_scale;
+    p.part_size = 64; p.num_parts = slots; p.part_o = (float *)a.workspace; p.part_ml = p.part_o + (int64_t)a.nq * a.H * slots * a.D; p.out = (half_t *)a.out;
+    dim3 grid((unsigned)nw), block(256);
+    if (a.D == 128) attn_share_fp8_mfma_kernel<128, 8><<<grid, block, 0, s>>>(p, a.tickets, a.nq);
+    else attn_share_fp8_mfma_kernel<64, 8><<<grid, block, 0, s>>>(p, a.tickets, a.nq);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "attn_share_fp8_mfma launch failed: %s", hipGetErrorString(e));
     return 0;
 }
 

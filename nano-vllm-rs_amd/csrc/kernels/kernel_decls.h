@@ -155,6 +155,9 @@ bool attn_share_fp8_ok(int D, int block_size);
 // plan (num_parts == 1: 16-bit rows; else partitions of part_size keys, a multiple of 64, as f32 partials for attention_fp8's merge); callers use attention_fp8
 bool attn_fp8_mfma_ok(int D, int H, int KVH, int block_size);
 int attn_fp8_mfma(const AttnFp8Args &a, int32_t part_size, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s);
+// ... and its work-balanced form (attn_share_fp8_mfma_kernel: 4 * nw waves walk equal shares of all pairs' 64-key steps; needs a.tickets, a.workspace with
+// `slots` >= ceil(max_ctx / 64) partial slots per (query, head), nq <= 1024); attention_fp8 takes it under the rule of the G <= 4 work-balanced launch
+int attn_share_fp8_mfma(const AttnFp8Args &a, int32_t slots, int32_t nw, hipStream_t s);
 
 bool flash_prefill_ok(int D, int H, int KVH);
 int flash_tile_positions(int H, int KVH);

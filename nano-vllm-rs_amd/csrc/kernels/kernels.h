@@ -60,7 +60,7 @@ struct AttnFp8Args {
     half_bits *out;                            // [nq, H, D] of the build's 16-bit type
     void *workspace; size_t workspace_bytes;   // split-KV partials (attn_workspace_bytes; bytes 0 = not checked)
     int32_t shared_len;                        // AttnArgs' shared-prefix pass (flash_shared_prefix_fp8; needs a workspace and a block_size that is a power of two >= 64)
-    int32_t balance_hint;                      // AttnArgs' work-balanced form (attn_share_fp8_kernel): > 0 = this many equal shares, wherever it can run
+    int32_t balance_hint;                      // AttnArgs' work-balanced form (attn_share_fp8_kernel; H/KVH = 8: attn_share_fp8_mfma_kernel, this many workgroups of 4 shares): > 0 = this many equal shares, wherever it can run
     unsigned int *tickets;                     // [nq * KVH] arrival counters of the work-balanced form, ZERO between launches (re-armed by the kernel); null = never taken
     const int32_t *shared_rows, *shared_kv0, *shared_count;   // as in AttnArgs: the group inside the batch (device arrays, all three or none)
 };

@@ -181,8 +181,9 @@ int nvr_model_runner::init() {                                       // ModelRun
         NVR_HIP_CHECK(hipMemset(attn_tickets, 0, (size_t)(max_seqs * KVH) * sizeof(unsigned int)));
     }
     // an fp8 runner's decode steps may take the work-balanced attention launch: the counters exist, the block size suits the kernel, NVR_ATTN_SHARE is not 0
-    // (8 query heads per kv head: the MFMA kernel has no work-balanced instance, its steps are per-pair launches)
-    share_fp8 = kv_fp8 && attn_tickets && env.attn_share != 0 && KD(attn_share_fp8_ok((int)D, (int)block_size)) && H / KVH != 8;
+    // (8 query heads per kv head: attn_share_fp8_mfma_kernel, wherever the MFMA decode kernel runs)
+    share_fp8 = kv_fp8 && attn_tickets && env.attn_share != 0 &&
+                (H / KVH == 8 ? KD(attn_fp8_mfma_ok((int)D, (int)H, (int)KVH, (int)block_size)) : KD(attn_share_fp8_ok((int)D, (int)block_size)));
     // step-input arena
     auto carve = [&](size_t &off, size_t bytes) { off = in_bytes; in_bytes += (bytes + 255) / 256 * 256; };
     // prefill region (the start of the arena): capacity for the largest step; a step lays its arrays out back to back for its own
@@ -805,10 +806,16 @@ bool nvr_model_runner::ragged_batch(size_t nseq, int64_t sum_ctx, int64_t max_ct
     // ... and only up to one pair per CU: the byte kernel has one workgroup resident per CU where the per-pair kernel has two, so from two pairs per CU on the
     // dispatcher balances the per-pair workgroups better than the static cut does (profiles/fp8_ragged.txt: 64 sequences x 8 kv heads of 64..4096 keys 2.47 per-pair
     // against 2.58 ms per step; 32 x 8 of 256..8192 keys 2.91 against 2.21)
-    if (kv_fp8 && pairs > cus) return false;
+    // 8 query heads per kv head (attn_share_fp8_mfma_kernel): two workgroups are resident there too, and two pairs per CU measured faster (profiles/fp8_gqa8_ragged.txt:
+    // 64 x 8 of 64..4096 keys 55.6 -> 42.5 us per layer)
+    const bool wide8 = kv_fp8 && H / KVH == 8;
+    if (kv_fp8 && pairs > (wide8 ? 2 : 1) * cus) return false;
     // ... and not below six units per CU in all: the step is then launch-bound and the per-pair launch's shorter ramp wins (12 sequences of 20..1500 keys: 1.08
-    // against 1.24 ms per step; 8 of 64..8192 keys — 2040 units — 1.65 -> 1.33 the other way)
-    return pairs <= 1024 && max_ctx * (int64_t)nseq * 100 >= sum_ctx * 130 && units >= 6 * cus;
+    // against 1.24 ms per step; 8 of 64..8192 keys — 2040 units — 1.65 -> 1.33 the other way).  8 query heads per kv head have floors of their own, the smallest
+    // measured wins: 8 units per CU at head_dim 128 (24 x 8 pairs of 200..1500 keys, 7.7 per CU: 19.7 -> 18.6 us per layer), 14 at head_dim 64 (7.7 per CU LOST,
+    // 12.9 -> 14.8; 13.8 per CU 20.8 -> 19.3)
+    const int64_t floor_units = wide8 ? (D >= 128 ? 8 : 14) : 6;
+    return pairs <= 1024 && max_ctx * (int64_t)nseq * 100 >= sum_ctx * 130 && units >= floor_units * cus;
 }
 
 // Prefill on tensor-parallel ranks as TWO micro-batches of whole sequences (row g, nvr_runner_set_tp_prefill_overlap(r, 2)): rows [0, mb_rows)
@@ -957,7 +964,8 @@ int nvr_model_runner::forward(int64_t T, int64_t B, bool is_prefill, int64_t max
             f.nq = (int32_t)T; f.H = (int32_t)H; f.KVH = (int32_t)KVH; f.D = (int32_t)D; f.scale = scale; f.k_scale = k_scale; f.v_scale = v_scale;
             f.max_ctx = (int32_t)max_ctx; f.out = attn; f.workspace = attn_ws; f.workspace_bytes = attn_ws_bytes;
             f.shared_len = (int32_t)decode_shared_len;
-            f.tickets = share_fp8 ? attn_tickets : nullptr; f.balance_hint = decode_ragged ? decode_shares : 0;
+            // (8 query heads per kv head: tickets only with a ragged batch — the launch rule's pair-count case lost there, 288 uniform pairs 28.7 -> 30.4 us per layer)
+            f.tickets = share_fp8 && (H / KVH != 8 || decode_ragged) ? attn_tickets : nullptr; f.balance_hint = decode_ragged ? decode_shares : 0;
             if (decode_shared_len > 0 && decode_shared_rows < T) {     // a group inside the batch: per-row kv0, member rows, member count
                 f.shared_kv0 = (const int32_t *)(in_dev + off_dec + dof_skv0); f.shared_rows = (const int32_t *)(in_dev + off_dec + dof_srows);
                 f.shared_count = (const int32_t *)(in_dev + off_dec + dof_scount);

@@ -99,7 +99,7 @@ struct nvr_model_runner {
     std::map<uint64_t, hipGraphExec_t> graphs;
     size_t last_rows = 0; bool last_prefill = false; int64_t last_tokens = 0;
     int64_t decode_shared_len = 0;                       // the last decode step: tokens its sharing group holds in the same leading blocks
-    bool share_fp8 = false;                              // kv_fp8: the work-balanced launch of attention_fp8 may be taken (attn_share_fp8_ok, tickets, NVR_ATTN_SHARE != 0)
+    bool share_fp8 = false;                              // kv_fp8: the work-balanced launch of attention_fp8 may be taken (attn_share_fp8_ok, or attn_fp8_mfma_ok at 8 heads per kv head; tickets, NVR_ATTN_SHARE != 0)
     bool decode_ragged = false;                         // the decode step's contexts are ragged enough for the work-balanced attention launch (ragged_batch)
     bool ragged_batch(size_t nseq, int64_t sum_ctx, int64_t max_ctx);   // (also sets decode_shares)
     int32_t decode_shares = 0;                           // ... and the number of shares its launch is asked for
