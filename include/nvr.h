@@ -110,7 +110,9 @@ typedef struct nvr_config {
                                           (prefix-cache hits, block_manager.rs:181-197; BASELINE configs[4]) attend to those blocks in one
                                           MFMA pass for the whole batch (nvr_paged_attn_decode_shared; kv_cache_dtype "fp8":
                                           nvr_paged_attn_decode_shared_fp8, when kvcache_block_size is a power of two >= 64) instead of once per
-                                          sequence; same results within the attention tolerance.  0 = default (32), < 0 = never */
+                                          sequence; same results within the attention tolerance.  0 = default (32; an fp8 cache at 8 query heads
+                                          per kv head: also sequences x shared keys >= 192 Ki at head_dim 128, 256 Ki at head_dim 64, the
+                                          measured crossover against its MFMA decode kernel), < 0 = never */
     char device[16];                   /* config.rs:48, validated like :108-111 plus "hip": "hip" (default) | "cuda" (the reference's
                                           default, taken as "the GPU") | "cpu" | "metal"; a runner exists only for "hip" / "cuda" —
                                           there is no CPU path in this library (NVR_ERR_UNSUPPORTED) */

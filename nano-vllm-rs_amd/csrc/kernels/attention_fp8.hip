@@ -17,7 +17,7 @@
 // Two launches: one or more workgroups per (query, kv head) pair (attn_fp8_kernel, + attn_fp8_merge_kernel for split contexts), or — pair counts that fill the
 // per-pair rounds badly, ragged batches — workgroups that walk equal shares of all pairs' keys (attn_share_fp8_kernel).  G = 8 does not run here: its
 // launches go to the matrix cores (attn_fp8_mfma_kernel per pair, attn_share_fp8_mfma_kernel work-balanced: attention_fp8_mfma.hip) with this file's partials,
-// merge kernel and launch rule.
+// merge kernel and launch rule, the shared-prefix plan included (launch_attn_fp8_mfma).
 #include <algorithm>
 #include <type_traits>
 #include "kernels.h"
@@ -722,7 +722,8 @@ static int launch_attn_fp8(const AttnFp8Args &a, hipStream_t s) {
 
 // G = 8 (attn_fp8_mfma_ok): attn_fp8_mfma_kernel (attention_fp8_mfma.hip) on the per-pair plan above — one workgroup per (query, kv head) from 192 pairs on,
 // else the context cut to reach ~256 workgroups — except that a partition keeps at least one 64-key step for each of the kernel's 4 waves; partitions
-// are whole 64-key steps, at most one per 64 keys of max_ctx (the workspace's cap); split contexts take the merge launch.
+// are whole 64-key steps, at most one per 64 keys of max_ctx (the workspace's cap); split contexts take the merge launch.  shared_len > 0: flash_shared_prefix_fp8
+// over the shared keys (partitions 0 .. sparts-1), attn_fp8_mfma_kernel<D, 8, true> over the keys behind them, always merged; never work-balanced.
 template <int D>
 static int launch_attn_fp8_mfma(const AttnFp8Args &a, hipStream_t s) {
     const int64_t mc = a.max_ctx > 0 ? a.max_ctx : 1, pairs = (int64_t)a.nq * a.KVH, units = (mc + 63) / 64;
@@ -736,18 +737,43 @@ static int launch_attn_fp8_mfma(const AttnFp8Args &a, hipStream_t s) {
         const int64_t nw = a.balance_hint > 0 ? a.balance_hint : share_mode() == 2 ? 2 * cus : cus;
         if ((by_count || a.balance_hint > 0 || share_mode() == 2) && pairs < 2048 && cap >= units) return attn_share_fp8_mfma(a, (int32_t)units, (int32_t)nw, s);
     }
-    int64_t want = 1;
-    if (a.workspace) want = pairs >= 192 ? 1 : (256 + pairs - 1) / pairs;
-    want = std::max<int64_t>(1, std::min<int64_t>(want, units / 4));
-    if (a.workspace_bytes) want = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)(a.workspace_bytes / ((size_t)a.nq * a.H * (D + 2) * sizeof(float)))));
-    const int64_t ps = ((mc + want - 1) / want + 63) / 64 * 64;
-    const int np = (int)((mc + ps - 1) / ps);
+    int64_t want = 1, ps;
+    int np, sparts = 0;
+    if (a.shared_len > 0) {
+        // launch_attn_fp8's plan on this function's rule: the shared keys [0, shared_len) in sparts equal partitions of whole 64-key steps until the
+        // tile launch (flash_shared_fp8_kernel<D, 8>: 16 decode rows x 8 heads per workgroup) has ~256 workgroups, at most half the workspace's slots;
+        // the keys behind them like a context of their own — one partition per pair from 192 pairs, else towards ~256 workgroups, a partition
+        // keeps a 64-key step for each of the 4 waves where there are that many; np >= 2: always merged.
+        const int qb = 16;                                                // 128 / G
+        const int64_t wgs = (int64_t)((a.nq + qb - 1) / qb) * a.KVH, n64 = a.shared_len / 64;
+        int64_t c = std::min<int64_t>(std::max<int64_t>(1, (256 + wgs - 1) / wgs), n64);
+        while (n64 % c) --c;
+        const int64_t rest = std::max<int64_t>(a.shared_rows ? mc : mc - a.shared_len, 64);   // a query outside the group reads its whole context
+        const int64_t cap = a.workspace_bytes ? (int64_t)(a.workspace_bytes / ((size_t)a.nq * a.H * (D + 2) * sizeof(float))) : units;
+        if (cap < 2) return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: workspace too small for the shared-prefix pass");
+        while (c > 1 && c > cap / 2) { --c; while (n64 % c) --c; }
+        sparts = (int)c;
+        want = pairs >= 192 ? 1 : (256 + pairs - 1) / pairs;
+        want = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, (rest + 63) / 64 / 4), cap - sparts));
+        ps = ((rest + want - 1) / want + 63) / 64 * 64;
+        np = sparts + (int)((rest + ps - 1) / ps);
+    } else {
+        if (a.workspace) want = pairs >= 192 ? 1 : (256 + pairs - 1) / pairs;
+        want = std::max<int64_t>(1, std::min<int64_t>(want, units / 4));
+        if (a.workspace_bytes) want = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)(a.workspace_bytes / ((size_t)a.nq * a.H * (D + 2) * sizeof(float)))));
+        ps = ((mc + want - 1) / want + 63) / 64 * 64;
+        np = (int)((mc + ps - 1) / ps);
+    }
     float *part_o = (float *)a.workspace, *part_ml = part_o + (int64_t)a.nq * a.H * np * D;
-    if (int rc = attn_fp8_mfma(a, (int32_t)ps, np, part_o, part_ml, s)) return rc;
+    if (sparts > 0)                                                      // partitions [0, sparts): the whole group's rows against each 64-key step once per tile
+        if (int rc = flash_shared_prefix_fp8(a.q, a.ldq, a.k, a.v, a.block_tables, a.max_blocks, a.block_size, a.nq, a.H, a.KVH, D, a.scale, a.k_scale, a.v_scale,
+                                             a.shared_len / sparts, sparts, np, part_o, part_ml, s, a.shared_rows, a.shared_count)) return rc;
+    if (int rc = attn_fp8_mfma(a, (int32_t)ps, np, part_o, part_ml, s, sparts)) return rc;
     if (np > 1) {
         const int64_t rows = (int64_t)a.H * a.nq;
-        attn_fp8_merge_kernel<D><<<dim3((unsigned)((rows + 256 / (D / 4) - 1) / (256 / (D / 4)))), dim3(256), 0, s>>>(part_o, part_ml, a.ctx_lens, a.H, (int)ps, np, 0, 0,
-                                                                                                                   nullptr, rows, (half_t *)a.out);
+        attn_fp8_merge_kernel<D><<<dim3((unsigned)((rows + 256 / (D / 4) - 1) / (256 / (D / 4)))), dim3(256), 0, s>>>(part_o, part_ml, a.ctx_lens, a.H, (int)ps, np, sparts,
+                                                                                                                   sparts ? a.shared_len : 0,
+                                                                                                                   sparts ? a.shared_kv0 : nullptr, rows, (half_t *)a.out);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "attention_fp8 (merge) launch failed: %s", hipGetErrorString(e));
     }
@@ -766,8 +792,8 @@ int attention_fp8(const AttnFp8Args &a, hipStream_t s) {
                              a.shared_len, a.block_size);
         if ((a.shared_rows != nullptr) != (a.shared_kv0 != nullptr) || (a.shared_rows != nullptr) != (a.shared_count != nullptr))
             return nvr::fail(NVR_ERR_INVALID_ARG, "attention_fp8: shared_rows / shared_kv0 / shared_count come together");
-        if (!flash_prefill_fp8_ok(a.D, a.H, a.KVH, a.block_size))
-            return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: the shared-prefix pass takes D in {64,128}, H/KVH in {1,2,4}, block_size a power of two >= 64 "
+        if (!flash_shared_fp8_ok(a.D, a.H, a.KVH, a.block_size))
+            return nvr::fail(NVR_ERR_UNSUPPORTED, "attention_fp8: the shared-prefix pass takes D in {64,128}, H/KVH in {1,2,4,8}, block_size a power of two >= 64 "
                              "(D=%d H=%d KVH=%d block_size=%d)", a.D, a.H, a.KVH, a.block_size);
     }
     if (G == 8 && attn_fp8_mfma_ok(a.D, a.H, a.KVH, a.block_size))      // wide groups: the MFMA kernels (per-pair launches, or with tickets and under the rule the work-balanced one)

@@ -31,8 +31,13 @@
 //
 // Bytes behind a context: the last step of a partition clamps its K and V rows to the last visible key (never READ: a NaN code times a zero
 // probability is NaN inside an MFMA), scores are masked by key INDEX, block-table entries past the context are not dereferenced.
+// Behind a shared prefix (OWN = true, a compile-time variant: the plain instantiation keeps its instructions): attn_fp8_kernel's part0 / kv0 / kv0_rows.  Slots
+// 0 .. part0-1 of a (query, head) belong to flash_shared_prefix_fp8 (flash_prefill_fp8.hip: the group's rows against the shared keys once per 16-row tile); this
+// launch has num_parts - part0 partitions per pair, partition part0 + i = keys [kv0_t + i·part_size, ..) with kv0_t = kv0_rows[t] or kv0 — a multiple of 64, so
+// a step still lies inside one block — and always leaves partials.  A member without own keys and a non-member shorter than a partition return as empty partitions.
 // End: the waves' (max, sum, Oᵀ) meet in LDS (each wave's own, drained ring) and are merged in wave order 0..3; a wave without a step contributes
 // (-inf, 0, 0) with weight 0; a query without keys writes a zero row; the order is fixed, so two launches agree bit for bit.
+#include <type_traits>
 #include "kernels.h"
 #include "device_utils.h"
 #include "flash_common.h"
@@ -56,9 +61,15 @@ struct AttnFp8MfmaParams {
     float *part_o, *part_ml;           // [nq, H, num_parts, D], [nq, H, num_parts, 2]
     half_t *out;                       // [nq, H, D]
 };
+// OWN: the keys behind a shared prefix (attn_fp8_kernel's fields of the same names): partitions 0..part0-1 hold the group's shared keys [0, kv0), written
+// by flash_shared_prefix_fp8; the launch covers partition part0 + i = keys [kv0_t + i*part_size, ..) of query t and always leaves partials
+struct AttnFp8MfmaOwnParams : AttnFp8MfmaParams {
+    int32_t part0, kv0;
+    const int32_t *kv0_rows;           // per-query kv0 (a group inside the batch: members shared_len, others 0) or null = kv0 for all
+};
 
-template <int D, int G>
-__global__ __launch_bounds__(256, 2) void attn_fp8_mfma_kernel(AttnFp8MfmaParams p) {
+template <int D, int G, bool OWN>
+__global__ __launch_bounds__(256, 2) void attn_fp8_mfma_kernel(std::conditional_t<OWN, AttnFp8MfmaOwnParams, AttnFp8MfmaParams> p) {
     static_assert(G >= 1 && G <= 16 && (D == 64 || D == 128), "the G heads of a kv head are the 16 columns of one MFMA");
     constexpr int KT = 64, WAVES = 4;            // keys per step; waves per workgroup
     constexpr int CPR = D / 16;                  // 16-byte chunks per row
@@ -70,12 +81,19 @@ __global__ __launch_bounds__(256, 2) void attn_fp8_mfma_kernel(AttnFp8MfmaParams
     static_assert((G * D + 2 * G) * 4 <= WRING, "the wave's partial fits its drained ring");
     __shared__ __attribute__((aligned(16))) char smem[WAVES * WRING];
 
-    const int part = blockIdx.x % p.num_parts, g = (blockIdx.x / p.num_parts) % p.KVH;
-    const int t = blockIdx.x / (p.num_parts * p.KVH);
+    int lparts = p.num_parts;                        // partitions of this launch
+    if constexpr (OWN) lparts -= p.part0;
+    int part = blockIdx.x % lparts;
+    const int g = (blockIdx.x / lparts) % p.KVH;
+    const int t = blockIdx.x / (lparts * p.KVH);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int r = lane & 15, g4 = lane >> 4;
-    const bool direct = p.num_parts == 1;
-    const int p0 = part * p.part_size;
+    const bool direct = !OWN && p.num_parts == 1;
+    int p0 = part * p.part_size;
+    if constexpr (OWN) {                             // (kv0: a multiple of 64, so a 64-key step still lies inside one block)
+        p0 += p.kv0_rows ? __builtin_amdgcn_readfirstlane(p.kv0_rows[t]) : p.kv0;
+        part += p.part0;
+    }
 
     // register copy of 64 block-table entries (lane j holds entry 64·c + j) by a load that waits for itself (flash_prefill_fp8.hip)
     int bt_reg = 0, bt_chunk = -1;
@@ -545,18 +563,27 @@ bool attn_fp8_mfma_ok(int D, int H, int KVH, int block_size) {
 
 // One launch of nq * KVH * num_parts workgroups; num_parts == 1: 16-bit rows into a.out, else partials into part_o / part_ml for attn_fp8_merge_kernel
 // (the partition plan and the merge launch: launch_attn_fp8_mfma, attention_fp8.hip)
-int attn_fp8_mfma(const AttnFp8Args &a, int32_t part_size, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s) {
-    if (!attn_fp8_mfma_ok(a.D, a.H, a.KVH, a.block_size) || num_parts < 1 || (num_parts > 1 && (part_size <= 0 || part_size % 64 || !part_o || !part_ml)))
-        return nvr::fail(NVR_ERR_UNSUPPORTED, "attn_fp8_mfma: D=%d H=%d KVH=%d block_size=%d, %d partitions of %d keys (D in {64,128}, H/KVH = 8, block_size a power "
-                         "of two >= 64, partitions of whole 64-key steps)", a.D, a.H, a.KVH, a.block_size, num_parts, part_size);
-    AttnFp8MfmaParams p{};
+// part0 > 0: the own keys behind a shared prefix — partitions part0 .. num_parts-1 from key a.shared_kv0[t] (or a.shared_len) on, partials always
+int attn_fp8_mfma(const AttnFp8Args &a, int32_t part_size, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s, int32_t part0) {
+    if (!attn_fp8_mfma_ok(a.D, a.H, a.KVH, a.block_size) || num_parts < 1 || (num_parts > 1 && (part_size <= 0 || part_size % 64 || !part_o || !part_ml)) ||
+        part0 < 0 || (part0 > 0 && (part0 >= num_parts || a.shared_len <= 0 || a.shared_len % 64)))
+        return nvr::fail(NVR_ERR_UNSUPPORTED, "attn_fp8_mfma: D=%d H=%d KVH=%d block_size=%d, %d partitions of %d keys, %d of them behind %d shared keys (D in {64,128}, "
+                         "H/KVH = 8, block_size a power of two >= 64, partitions and shared keys of whole 64-key steps)", a.D, a.H, a.KVH, a.block_size, num_parts,
+                         part_size, num_parts - part0, a.shared_len);
+    AttnFp8MfmaOwnParams p{};
     p.q = (const half_t *)a.q; p.ldq = a.ldq; p.k = a.k; p.v = a.v; p.ctx_lens = a.ctx_lens; p.block_tables = a.block_tables;
     p.max_blocks = a.max_blocks; p.block_size = a.block_size; p.bs_shift = __builtin_ctz(a.block_size);
     p.H = a.H; p.KVH = a.KVH; p.scale = a.scale * a.k_scale; p.v_scale = a.v_scale;
     p.part_size = num_parts > 1 ? part_size : 0x3fffffc0; p.num_parts = num_parts; p.part_o = part_o; p.part_ml = part_ml; p.out = (half_t *)a.out;
-    dim3 grid((unsigned)((int64_t)a.nq * a.KVH * num_parts)), block(256);
-    if (a.D == 128) attn_fp8_mfma_kernel<128, 8><<<grid, block, 0, s>>>(p);
-    else attn_fp8_mfma_kernel<64, 8><<<grid, block, 0, s>>>(p);
+    p.part0 = part0; p.kv0 = a.shared_len; p.kv0_rows = a.shared_kv0;
+    dim3 grid((unsigned)((int64_t)a.nq * a.KVH * (num_parts - part0))), block(256);
+    if (part0 > 0) {
+        if (a.D == 128) attn_fp8_mfma_kernel<128, 8, true><<<grid, block, 0, s>>>(p);
+        else attn_fp8_mfma_kernel<64, 8, true><<<grid, block, 0, s>>>(p);
+    } else {
+        if (a.D == 128) attn_fp8_mfma_kernel<128, 8, false><<<grid, block, 0, s>>>(p);
+        else attn_fp8_mfma_kernel<64, 8, false><<<grid, block, 0, s>>>(p);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "attn_fp8_mfma launch failed: %s", hipGetErrorString(e));
     return 0;

@@ -39,7 +39,8 @@
 // or beyond the context — garbage, e4m3 NaN codes included — are never READ, let alone multiplied by a zero probability; block-table entries
 // past the context are never dereferenced.
 //
-// flash_shared_fp8_kernel (below): the same data path for the decode step's shared-prefix pass — decode rows in place of positions, no causal part.
+// flash_shared_fp8_kernel (below): the same data path for the decode step's shared-prefix pass — decode rows in place of positions, no causal part;
+// G in {1, 2, 4} on the prefill tile, and G = 8 on a tile of its own (16 rows x 8 heads, two heads per wave).
 #include <type_traits>
 #include "kernels.h"
 #include "device_utils.h"
@@ -342,6 +343,9 @@ int flash_prefill_fp8(const FlashFp8Args &a, hipStream_t s) {
 //     maximum x softmax scale x k_scale), the sum of the 16-bit-rounded probabilities.
 // 2-slot ring and two workgroups per CU as in the prefill kernel: a launch is ~256 workgroups of part_len / 64 (2 at BASELINE configs[4])
 // steps, so step 1 is requested while step 0 is computed and nothing deeper could be in flight; other depths: not measured.
+// G = 8 (the prefill kernel has no such instantiation): the tile is 16 decode rows x the 8 heads of a kv head, ALL FOUR waves hold the same 16
+// rows and wave w owns heads 8g + 2w and 8g + 2w + 1, one 16-row query tile per head, so the member-row lookup is one per lane.  (Tile height 16 against 32
+// rows: profiles/fp8_gqa8_shared.txt.)
 struct FlashFp8SharedParams {
     const half_t *q; int64_t ldq;
     const uint8_t *k, *v;
@@ -382,11 +386,15 @@ __global__ __launch_bounds__(256, 2) void flash_shared_fp8_kernel(FlashFp8Shared
         int pblk;
         if (G == 1) { head[t] = g; pblk = wave * 2 + t; }
         else if (G == 2) { head[t] = g * 2 + t; pblk = wave; }
-        else { head[t] = g * 4 + (wave & 1) * 2 + t; pblk = wave >> 1; }
-        const int qi = pblk * 16 + r;
-        qvalid[t] = qi < nq;
-        const int qc = row0 + (qvalid[t] ? qi : nq - 1);
-        qrow[t] = p.srows ? p.srows[qc] : qc;
+        else if (G == 4) { head[t] = g * 4 + (wave & 1) * 2 + t; pblk = wave >> 1; }
+        else { head[t] = g * 8 + wave * 2 + t; pblk = 0; }               // G = 8: all four waves hold the same 16 rows, two heads each
+        if (G == 8 && t == 1) { qvalid[1] = qvalid[0]; qrow[1] = qrow[0]; }   // the row of the lane's other head: looked up once
+        else {
+            const int qi = pblk * 16 + r;
+            qvalid[t] = qi < nq;
+            const int qc = row0 + (qvalid[t] ? qi : nq - 1);
+            qrow[t] = p.srows ? p.srows[qc] : qc;
+        }
         const half_t *qptr = p.q + (int64_t)qrow[t] * p.ldq + (int64_t)head[t] * D + g4 * 8;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) qf[t][ks] = *reinterpret_cast<const half8_t *>(qptr + ks * 32);
@@ -540,6 +548,13 @@ __global__ __launch_bounds__(256, 2) void flash_shared_fp8_kernel(FlashFp8Shared
     }
 }
 
+// shapes of the shared-prefix pass: the prefill kernel's, or 8 heads per kv head (the tile of 16 decode rows x 8 heads)
+bool flash_shared_fp8_ok(int D, int H, int KVH, int block_size) {
+    if (flash_prefill_fp8_ok(D, H, KVH, block_size)) return true;
+    if (KVH <= 0 || H % KVH) return false;
+    return (D == 64 || D == 128) && H / KVH == 8 && block_size >= 64 && (block_size & (block_size - 1)) == 0;
+}
+
 // Partitions 0 .. sparts-1 (part_len keys each) of a decode step whose sequences (all nq, or the rows[0 .. *count) of them) share their first
 // sparts * part_len cached keys: f32 partials into slots (row, head, partition) of part_o [nq, H, num_parts, D] / part_ml [nq, H, num_parts, 2]
 int flash_shared_prefix_fp8(const half_bits *q, int64_t ldq, const uint8_t *k_cache, const uint8_t *v_cache, const int32_t *block_tables,
@@ -547,7 +562,7 @@ int flash_shared_prefix_fp8(const half_bits *q, int64_t ldq, const uint8_t *k_ca
                             float v_scale, int32_t part_len, int32_t sparts, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s,
                             const int32_t *rows, const int32_t *count) {
     if (nq == 0) return 0;
-    if (!flash_prefill_fp8_ok(D, H, KVH, block_size) || part_len <= 0 || part_len % 64 || sparts < 1 || sparts > num_parts)
+    if (!flash_shared_fp8_ok(D, H, KVH, block_size) || part_len <= 0 || part_len % 64 || sparts < 1 || sparts > num_parts)
         return nvr::fail(NVR_ERR_UNSUPPORTED, "flash_shared_prefix_fp8: D=%d H=%d KVH=%d block_size=%d part_len=%d x %d", D, H, KVH, block_size, part_len, sparts);
     FlashFp8SharedParams p{};
     p.q = (const half_t *)q; p.ldq = ldq; p.k = k_cache; p.v = v_cache;
@@ -557,7 +572,7 @@ int flash_shared_prefix_fp8(const half_bits *q, int64_t ldq, const uint8_t *k_ca
     const int G = H / KVH, qb = 128 / G;
     dim3 grid((unsigned)((int64_t)((nq + qb - 1) / qb) * KVH), (unsigned)sparts), block(256);
 #define NVR_FLASH8_S(DD, GG) if (D == DD && G == GG) flash_shared_fp8_kernel<DD, GG><<<grid, block, 0, s>>>(p);
-    NVR_FLASH8_S(128, 1) NVR_FLASH8_S(128, 2) NVR_FLASH8_S(128, 4) NVR_FLASH8_S(64, 1) NVR_FLASH8_S(64, 2) NVR_FLASH8_S(64, 4)
+    NVR_FLASH8_S(128, 1) NVR_FLASH8_S(128, 2) NVR_FLASH8_S(128, 4) NVR_FLASH8_S(128, 8) NVR_FLASH8_S(64, 1) NVR_FLASH8_S(64, 2) NVR_FLASH8_S(64, 4) NVR_FLASH8_S(64, 8)
 #undef NVR_FLASH8_S
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return nvr::fail(NVR_ERR_HIP, "flash_shared_prefix_fp8 launch failed: %s", hipGetErrorString(e));

@@ -152,9 +152,10 @@ int attention_fp8(const AttnFp8Args &a, hipStream_t s);
 // the work-balanced form of attention_fp8 can run: block_size a power of two >= the kernel's chunk (16 keys at D = 128, 32 at D = 64)
 bool attn_share_fp8_ok(int D, int block_size);
 // H/KVH = 8 on the matrix cores (attention_fp8_mfma.hip): D in {64,128}, block_size a power of two >= 64.  attn_fp8_mfma: the kernel's launch alone, on a given
-// plan (num_parts == 1: 16-bit rows; else partitions of part_size keys, a multiple of 64, as f32 partials for attention_fp8's merge); callers use attention_fp8
+// plan (num_parts == 1: 16-bit rows; else partitions of part_size keys, a multiple of 64, as f32 partials for attention_fp8's merge; part0 > 0: only the
+// partitions part0 .. num_parts-1, which start behind the a.shared_kv0[t] / a.shared_len keys that flash_shared_prefix_fp8 covers); callers use attention_fp8
 bool attn_fp8_mfma_ok(int D, int H, int KVH, int block_size);
-int attn_fp8_mfma(const AttnFp8Args &a, int32_t part_size, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s);
+int attn_fp8_mfma(const AttnFp8Args &a, int32_t part_size, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s, int32_t part0 = 0);
 // ... and its work-balanced form (attn_share_fp8_mfma_kernel: 4 * nw waves walk equal shares of all pairs' 64-key steps; needs a.tickets, a.workspace with
 // `slots` >= ceil(max_ctx / 64) partial slots per (query, head), nq <= 1024); attention_fp8 takes it under the rule of the G <= 4 work-balanced launch
 int attn_share_fp8_mfma(const AttnFp8Args &a, int32_t slots, int32_t nw, hipStream_t s);
@@ -169,7 +170,10 @@ int flash_shared_prefix(const half_bits *q, int64_t ldq, const half_bits *k_cach
 // paged flash prefill over byte caches: D in {64,128}, H/KVH in {1,2,4}, block_size a power of two and a multiple of the 64-key step
 bool flash_prefill_fp8_ok(int D, int H, int KVH, int block_size);
 int flash_prefill_fp8(const FlashFp8Args &a, hipStream_t s);
-// flash_shared_prefix over byte caches: f32 partials (x v_scale, maximum in units of scale x k_scale) of partitions 0 .. sparts-1
+// flash_shared_prefix over byte caches: f32 partials (x v_scale, maximum in units of scale x k_scale) of partitions 0 .. sparts-1.
+// flash_shared_fp8_ok: flash_prefill_fp8_ok, or H/KVH = 8 with D in {64,128} and block_size a power of two >= 64 (a tile of its own: 16 decode rows x the
+// 8 heads of a kv head; the grid is ceil(nq / (128 / G)) * KVH x sparts for every G)
+bool flash_shared_fp8_ok(int D, int H, int KVH, int block_size);
 int flash_shared_prefix_fp8(const half_bits *q, int64_t ldq, const uint8_t *k_cache, const uint8_t *v_cache, const int32_t *block_tables,
                             int32_t max_blocks, int32_t block_size, int32_t nq, int32_t H, int32_t KVH, int32_t D, float scale, float k_scale,
                             float v_scale, int32_t part_len, int32_t sparts, int32_t num_parts, float *part_o, float *part_ml, hipStream_t s,

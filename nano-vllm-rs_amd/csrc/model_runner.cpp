@@ -736,7 +736,9 @@ int64_t nvr_model_runner::shared_prefix_plan(nvr_seq *const *seqs, size_t nseq, 
     if (f32) return 0;
     const int64_t min_seqs = cfg.shared_prefix_min_seqs == 0 ? 32 : cfg.shared_prefix_min_seqs;
     if (min_seqs < 0 || (int64_t)nseq < min_seqs || nseq < 2) return 0;
-    if (block_size < 64 || (block_size & (block_size - 1)) || !KD(flash_prefill_ok((int)D, (int)H, (int)KVH))) return 0;
+    if (block_size < 64 || (block_size & (block_size - 1))) return 0;
+    // (the byte cache's pass also takes 8 heads per kv head: a tile of its own)
+    if (!(kv_fp8 ? KD(flash_shared_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size)) : KD(flash_prefill_ok((int)D, (int)H, (int)KVH)))) return 0;
     auto full_blocks = [&](const nvr_seq &s) {                            // full blocks below the token of this step
         return std::min<size_t>(s.block_table.size(), (size_t)(((int64_t)s.len() - 1) / block_size));
     };
@@ -783,6 +785,18 @@ int64_t nvr_model_runner::shared_prefix_plan(nvr_seq *const *seqs, size_t nseq, 
     for (size_t b = (size_t)m; b < nseq; ++b) rows[b] = rows[0];
     *count = (int32_t)m; *members = m;
     return S;
+}
+
+// An fp8 runner keeps the plan when the byte cache's pass takes the shape (flash_shared_fp8_ok) and, at 8 heads per kv head, when it pays.  There the
+// plain route is the MFMA kernel, which already reads a key once for 8 heads, and the pass has a floor of its own (tile launch + own-key launch + merge
+// launch).  Measured (profiles/fp8_gqa8_shared.txt; H = 64, KVH = 8, 94 own keys; crossover in member rows): head_dim 128: ~384 rows behind 512 shared
+// keys, ~96 behind 1024, < 64 behind 2048; head_dim 64: ~512, ~200, ~80.  Held as rows x shared keys >= 192 Ki at head_dim 128 and 256 Ki at head_dim 64
+// (no measured loss is kept; the wins forfeited are 0.76-0.86x at exactly 128 Ki, head_dim 128).  A shared_prefix_min_seqs the caller has set is taken
+// as it is.  The answer reaches a captured step through the shared length of the graph key.
+bool nvr_model_runner::fp8_shared_plan_ok(int64_t shared_len, int64_t rows) const {
+    if (shared_len <= 0 || !KD(flash_shared_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size))) return false;
+    if (H / KVH != 8 || cfg.shared_prefix_min_seqs != 0) return true;
+    return rows * shared_len >= (D == 128 ? 192 : 256) * 1024;
 }
 
 // a captured decode step is a function of (batch size, context bucket, shared-prefix length, whole batch or a group of it, logits wanted)
@@ -1193,11 +1207,11 @@ int nvr_model_runner::execute(nvr_seq *const *seqs, size_t nseq, bool is_prefill
         T = (int64_t)nseq;
         decode_shared_len = shared_prefix_plan(seqs, nseq, (int32_t *)(hd + dof_skv0), (int32_t *)(hd + dof_srows), (int32_t *)(hd + dof_scount),
                                                &decode_shared_rows);
+        // attention_fp8's shared pass takes whole 64-key steps of one block (and at 8 heads per kv head only pays from a size on), its work-balanced form
+        // some block sizes only.  A plan is dropped BEFORE ragged_batch sees it: a batch that keeps the plain launches is judged as one without a prefix.
+        if (kv_fp8 && !fp8_shared_plan_ok(decode_shared_len, decode_shared_rows)) { decode_shared_len = 0; decode_shared_rows = 0; }
         decode_ragged = ragged_batch(nseq, sum_ctx, (cfg.enforce_eager || graphs_disabled) ? max_ctx : (max_ctx + 255) / 256 * 256);
-        if (kv_fp8) {                                        // attention_fp8's work-balanced form takes some block sizes only, and its shared pass takes whole 64-key steps of one block
-            decode_ragged = decode_ragged && share_fp8;
-            if (!KD(flash_prefill_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size))) { decode_shared_len = 0; decode_shared_rows = 0; }
-        }
+        if (kv_fp8) decode_ragged = decode_ragged && share_fp8;
     }
     // one H2D per array actually used this step (K19)
     auto up = [&](size_t off, size_t bytes) { return hipMemcpyAsync(in_dev + off, in_host + off, bytes, hipMemcpyHostToDevice, stream); };
@@ -1291,11 +1305,9 @@ int nvr_model_runner::execute_decode_ahead(nvr_seq *const *seqs, size_t nseq, in
     }
     decode_shared_len = shared_prefix_plan(seqs, nseq, (int32_t *)(hd + dof_skv0), (int32_t *)(hd + dof_srows), (int32_t *)(hd + dof_scount),
                                            &decode_shared_rows);
+    if (kv_fp8 && !fp8_shared_plan_ok(decode_shared_len, decode_shared_rows)) { decode_shared_len = 0; decode_shared_rows = 0; }   // (before ragged_batch, as in execute)
     decode_ragged = ragged_batch(nseq, sum_ctx, (cfg.enforce_eager || graphs_disabled) ? max_ctx : (max_ctx + 255) / 256 * 256);
-    if (kv_fp8) {
-        decode_ragged = decode_ragged && share_fp8;
-        if (!KD(flash_prefill_fp8_ok((int)D, (int)H, (int)KVH, (int)block_size))) { decode_shared_len = 0; decode_shared_rows = 0; }
-    }
+    if (kv_fp8) decode_ragged = decode_ragged && share_fp8;
     NVR_HIP_CHECK(hipMemcpyAsync(in_dev + off_dec + dof_pos, hd + dof_pos, dof_bt + nseq * max_blocks_per_seq * 4 - dof_pos, hipMemcpyHostToDevice, stream));
     last_rows = nseq; last_prefill = false; last_tokens = (int64_t)nseq;
     lm_parts = plan_lm_parts((int64_t)nseq);

@@ -64,7 +64,7 @@ struct nvr_model_runner {
     // nvr_config.kv_cache_dtype = "fp8": the pool holds OCP e4m3 bytes, value = byte * scale (kernels/attention_fp8.hip).  The projection launches of a
     // step get no_slots (all -1: they store no cache row) and one kv_store_fp8 launch per layer quantises the roped K / V columns of qkv; prefill attention
     // of whole prompts reads qkv, behind a cached prefix or in a later chunk it is flash_prefill_fp8 over the bytes; decode attention is attention_fp8
-    // (with its shared-prefix pass when flash_prefill_fp8_ok holds).
+    // (with its shared-prefix pass when fp8_shared_plan_ok holds).
     bool kv_fp8 = false, stepped = false;  // stepped: a step has been executed (the scales are fixed from then on)
     float k_scale = 1.f, v_scale = 1.f;
     int32_t *no_slots = nullptr;           // [max(max_tokens, max_seqs)] of -1
@@ -170,6 +170,7 @@ private:
     // sharing group of a decode batch (0 = none / too small: plain paged attention); fills kv0[nseq], rows[nseq], *count of the arena
     int64_t shared_prefix_plan(nvr_seq *const *seqs, size_t nseq, int32_t *kv0, int32_t *rows, int32_t *count, int64_t *members) const;
     mutable std::vector<int32_t> plan_keys, plan_cnt;    // scratch of the plan (first-block id -> count)
+    bool fp8_shared_plan_ok(int64_t shared_len, int64_t rows) const;   // kv_fp8: the byte cache's shared pass takes the plan (shape; at 8 heads per kv head: pays)
     bool prefill_kv_cache = false;                  // whole-prompt prefill whose K/V the flash kernel reads from the (contiguous) cache rows
     bool prefill_paged = false;                          // this prefill step skips cached prefixes (K/V via block tables)
     bool lazy_logits = true, want_logits = true, logits_valid = true; const uint16_t *lm_input = nullptr;

@@ -1,5 +1,5 @@
 """Shared-prefix decode attention over the FP8 KV cache at the BASELINE configs[4] shape (profiles/fp8_shared_prefix.txt).
-python tools/fp8_shared_bench.py [kernel] [engine]
+python tools/fp8_shared_bench.py [kernel] [engine] [gqa8]
 
 kernel: B = 512 sequences behind one 512-token prompt (2 shared blocks of 256) + 94 own keys each, H = 16, KVH = 8, D = 128: device events around
 replays of a hipGraph of 28 launches over 28 distinct layer caches (nothing re-read from the infinity cache), three alternating rounds of
@@ -7,7 +7,10 @@ replays of a hipGraph of 28 launches over 28 distinct layer caches (nothing re-r
   shared   nvr_paged_attn_decode_shared_fp8
   shared16 nvr_paged_attn_decode_shared over a 16-bit cache
 engine: Qwen3-0.6B random-init, kv_cache_dtype = "fp8", 512 x (512 shared + 64 own) prompt tokens, hipGraph + launch-ahead, ms per decode step with
-shared_prefix_min_seqs at its default and at -1, two alternating rounds."""
+shared_prefix_min_seqs at its default and at -1, two alternating rounds.
+gqa8: the kernel measurement at 8 query heads per kv head (profiles/fp8_gqa8_shared.txt): H = 64, KVH = 8, D in {128, 64}, 512 and 64 sequences behind 512 and
+2048 shared keys + 94 own keys each; plain = the per-pair MFMA launch without tickets, which is what an engine with shared_prefix_min_seqs = -1 launches.
+Further arguments narrow or widen the sweep: d128 | d64, b<sequences> .., p<shared blocks of 256 keys> .. (e.g. gqa8 b96 b128 b192 b256 b384 p2 p4 p8)."""
 import ctypes as C, gc, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, nvr_import
@@ -15,7 +18,7 @@ nvr = nvr_import.load(); l = nvr.lib(); nvr.check(l.nvr_device_set(0))
 what = sys.argv[1:] or ["kernel", "engine"]
 
 
-def kernel_times(B=512, H=16, KVH=8, D=128, BS=256, P=2, own=94, L=28, replays=20):
+def kernel_times(B=512, H=16, KVH=8, D=128, BS=256, P=2, own=94, L=28, replays=20, with16=True):
     st = C.c_void_p(); nvr.check(l.nvr_stream_create(C.byref(st)))
     rng = np.random.default_rng(3)
     NB, S = P + B, P * BS
@@ -29,9 +32,9 @@ def kernel_times(B=512, H=16, KVH=8, D=128, BS=256, P=2, own=94, L=28, replays=2
     ws = nvr.DeviceBuffer(l.nvr_paged_attn_workspace_bytes(B, H, D, S + own + BS))
     n = NB * BS * KVH * D
     h8 = (rng.integers(0, 0x48, n, dtype=np.uint8) | (rng.integers(0, 2, n, dtype=np.uint8) << 7))      # |value| < 4, no NaN code
-    h16 = rng.standard_normal(n, dtype=np.float32).astype(np.float16)
+    h16 = rng.standard_normal(n, dtype=np.float32).astype(np.float16) if with16 else None
     c8 = [(nvr.DeviceBuffer.from_numpy(h8), nvr.DeviceBuffer.from_numpy(h8)) for _ in range(L)]
-    c16 = [(nvr.DeviceBuffer.from_numpy(h16), nvr.DeviceBuffer.from_numpy(h16)) for _ in range(L)]
+    c16 = [(nvr.DeviceBuffer.from_numpy(h16), nvr.DeviceBuffer.from_numpy(h16)) for _ in range(L if with16 else 0)]
     scale = float(1 / np.sqrt(D))
     routes = {
         "plain": lambda i: l.nvr_paged_attn_decode_fp8(q.ptr, H * D, c8[i][0].ptr, c8[i][1].ptr, C.byref(meta), H, KVH, D, BS, scale, 1.0, 1.0, out.ptr, ws.ptr, None, st),
@@ -40,6 +43,8 @@ def kernel_times(B=512, H=16, KVH=8, D=128, BS=256, P=2, own=94, L=28, replays=2
         "shared16": lambda i: l.nvr_paged_attn_decode_shared(q.ptr, H * D, c16[i][0].ptr, c16[i][1].ptr, C.byref(meta), H, KVH, D, BS, scale, S, None, None, None,
                                                              out.ptr, ws.ptr, st),
     }
+    if not with16:
+        del routes["shared16"]
     graphs = {}
     for name, fn in routes.items():
         nvr.check(l.nvr_graph_capture_begin(st))
@@ -85,6 +90,14 @@ def engine_step_ms(min_seqs, nseq=512, steps=24):
 
 if "kernel" in what:
     kernel_times()
+if "gqa8" in what:
+    pick = lambda c, dflt: [int(w[1:]) for w in what if w[0] == c and w[1:].isdigit()] or dflt   # d128 | d64, b<sequences>.., p<shared blocks of 256>..
+    for D in pick("d", [128, 64]):
+        for B in pick("b", [512, 64]):
+            for P in pick("p", [2, 8]):
+                print(f"H=64 KVH=8 D={D}: {B} sequences behind {P * 256} shared keys + 94 own", flush=True)
+                kernel_times(B=B, H=64, KVH=8, D=D, P=P, with16=False)
+                gc.collect()
 if "engine" in what:
     for rnd in range(2):
         print(f"round {rnd}: " + ", ".join("shared_prefix_min_seqs=%d: %.3f ms per step (shared length %d)" % ((ms,) + engine_step_ms(ms)) for ms in (0, -1)), flush=True)
